@@ -6,6 +6,12 @@
 
 The timed region -- exactly K trials between two barrier + synchronize pairs -- is run R = --regions (7) times, every time from the
 restored initial parameters; `ms_per_step` / `value` are the MEDIAN region's, min / max beside them (`steps` stays the per-region count).
+A region whose LM loop reaches its own stop before K trials goes on from the restored initial parameters until it has run exactly K.
+
+--dump-outputs DIR writes, after the timed regions, what the last region's ba_minimize() leaves to its caller, as float64 .npy files:
+cams.npy (N x 15, the solver's camera state), points.npy (M x 3; for N > 1 the ranks' shards gathered in point order) and
+lm_result.npy ([final energy, lambda, status, iterations, trials] of the last ba_minimize() call).  The inputs are fixed by the
+arguments (a BAL file or a seeded synthetic problem), so two builds can be compared output for output.
 
 A "step" is one Levenberg-Marquardt trial = one row of the reference's iteration table
 (src/Eigen_ext/BacktrackLevMarqCholesky.h:308,322): point elimination, Schur assembly, dense LDL^T + solve,
@@ -157,6 +163,30 @@ def cpu_baseline(name, prob, budget_s=20.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, solver, prob, res, rank, world, dist):
+    """The state the last timed ba_minimize() left on the device, as float64 .npy files under `path` (rank 0 writes)."""
+    import numpy as np
+    import bundleadjustment_benchmarks_amd as ba
+    pts = solver.get(ba.GET_POINTS).reshape(-1, 3)
+    if world > 1:
+        shards = [None] * world
+        dist.all_gather_object(shards, (solver.p0, pts))
+        pts = np.concatenate([p for _, p in sorted(shards, key=lambda sp: sp[0])])
+    if rank != 0:
+        return
+    out = {"cams": solver.get(ba.GET_CAMS).reshape(prob.N, 15), "points": pts,
+           "lm_result": np.array([res["energy"], res["lam"], res["status"], res["iterations"], res["trials"]], np.float64)}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: the outputs of this workload (%d bytes) exceed the dump limit of %d" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -220,9 +250,13 @@ def main():
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--phase-reps", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write the outputs of the last one as DIR/<name>.npy (float64)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="no GPU: start the ranks, let them meet (gloo), print who met -- the launch path of --gpus N without the solver")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -280,13 +314,26 @@ def main():
     # warmup: W untimed trials, then restore the initial parameters (inputs stay resident in HBM)
     if args.warmup > 0:
         solver.minimize(max_trials=args.warmup, trace=False)
+
+    def run_steps(k):
+        """Exactly k trials from the restored start; an LM loop that stops on its own first starts again from there."""
+        done, res = 0, None
+        while done < k:
+            if done:
+                solver.set_state(cam0.reshape(prob.N, 15), pts0)
+            res = solver.minimize(max_trials=k - done, trace=False)
+            if res["trials"] < 1:
+                raise SystemExit("bench.py: ba_minimize ran no trial (status %s)" % ba.STATUS.get(res["status"], res["status"]))
+            done += res["trials"]
+        return done, res
+
     regions = []
     for _ in range(max(args.regions, 1)):  # every region: exactly K trials from the restored start, barrier + synchronize on both sides
         solver.set_state(cam0.reshape(prob.N, 15), pts0)
         solver.timing(reset=True)
         barrier()
         t0 = time.perf_counter()
-        res = solver.minimize(max_trials=args.steps, trace=False)
+        done, res = run_steps(args.steps)
         barrier()
         el = time.perf_counter() - t0
         if world > 1:
@@ -294,10 +341,11 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         tmr = solver.timing()
-        regions.append((el / max(res["trials"], 1), el, res, tmr))
+        regions.append((el / done, el, res, tmr, done))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, prob, res, rank, world, dist)
     order = sorted(range(len(regions)), key=lambda q: regions[q][0])
-    _, el, res, tm = regions[order[len(order) // 2]]  # the median region (all regions replay the same trials: same res)
-    steps_done = res["trials"]
+    _, el, res, tm, steps_done = regions[order[len(order) // 2]]  # the median region (all regions replay the same trials: same res)
     ms_all = [1e3 * w[0] for w in regions]
     dev_all = [w[3]["trial_ms"] / max(w[3]["n_trials"], 1) for w in regions]
 

@@ -1,10 +1,13 @@
 """bench.py's own launcher for --gpus N: started plain, it must start N rank processes before making any GPU
 call, let them meet, print ONE JSON line from rank 0, and fail loudly -- non-zero exit code, the failing rank's stderr -- when a rank
-fails.  No GPU here: --dry-launch stops behind the rendezvous; the failure case uses the ranks' own "no MI355X" exit."""
+fails.  No GPU here: --dry-launch stops behind the rendezvous; the failure case uses the ranks' own "no MI355X" exit.  The gpu-marked
+test at the end pins --steps and --dump-outputs on the solver itself."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 from conftest import ROOT
 
@@ -40,7 +43,6 @@ def test_three_ranks_meet_under_torch_distributed_run_too():
 def test_a_failing_rank_fails_the_launch_with_its_stderr():
     import torch
     if torch.cuda.is_available():
-        import pytest
         pytest.skip("needs a box without a GPU: the ranks' failure here is their own 'no MI355X' exit")
     out = run("--gpus", "2", "--steps", "2", "--warmup", "0")
     assert out.returncode != 0
@@ -51,3 +53,29 @@ def test_a_failing_rank_fails_the_launch_with_its_stderr():
 def test_world_size_mismatch_is_refused():
     out = run("--gpus", "2", "--dry-launch", env={"WORLD_SIZE": "3", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29534"})
     assert out.returncode != 0 and "WORLD_SIZE=3" in out.stderr
+
+
+@pytest.mark.gpu
+def test_steps_are_exact_and_outputs_are_dumped(tmp_path):
+    """--steps K times exactly K trials, also past the LM loop's own stop (cfg2 stops after ~220 trials), and --dump-outputs writes the
+    last timed run's state; two runs with the same workload and steps dump the same arrays bit for bit (--regions does not matter)."""
+    import numpy as np
+    dumps = []
+    for regions in ("1", "2"):
+        d = tmp_path / ("r" + regions)
+        out = run("--gpus", "1", "--workload", "cfg2", "--steps", "300", "--warmup", "2", "--regions", regions, "--no-cpu-baseline",
+                  "--phase-reps", "2", "--dump-outputs", str(d))
+        assert out.returncode == 0, out.stderr[-4000:]
+        lines = [w for w in out.stdout.splitlines() if w.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 300 and r["ms_per_step"] > 0
+        a = {n: np.load(d / (n + ".npy")) for n in ("cams", "points", "lm_result")}
+        assert all(v.dtype == np.float64 for v in a.values())
+        assert a["cams"].shape == (21, 15) and a["points"].shape == (11315, 3) and a["lm_result"].shape == (5,)
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert np.isfinite(a["points"]).all() and a["lm_result"][0] == r["final_energy"]
+        assert a["lm_result"][4] < 300, "the LM loop did not stop on its own: the restart path was not exercised"
+        dumps.append(a)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

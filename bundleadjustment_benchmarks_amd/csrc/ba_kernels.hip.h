@@ -898,14 +898,13 @@ __global__ __launch_bounds__(256) void k_more_build(int K, int Ml, int D, const 
 }
 // the tail of that matrix (shard 0 only): R22 | c2 from the outer factorisation (R22buf: D x (D + 1), column-major ld D), sqrt(lambda) I_D
 template <typename T>
-__global__ __launch_bounds__(256) void k_more_tail(int Ml, int D, const T *__restrict__ R22buf, const T *__restrict__ lam, T *__restrict__ A, size_t lda, T dbg_scale = (T)1)
+__global__ __launch_bounds__(256) void k_more_tail(int Ml, int D, const T *__restrict__ R22buf, const T *__restrict__ lam, T *__restrict__ A, size_t lda)
 {
     const int c = blockIdx.x; // column 0 .. D (D = the right-hand side)
-    size_t rR = 6 * (size_t)Ml, rL = rR + (size_t)D;
-    if (dbg_scale < (T)0) { dbg_scale = -dbg_scale; rL = rR; rR = rL + (size_t)D; } // (experiment: the sqrt(lambda) rows in front of R22)
+    const size_t rR = 6 * (size_t)Ml, rL = rR + (size_t)D;
     const int top = c < D ? c : D - 1;
     for (int i = threadIdx.x; i <= top; i += 256) A[(size_t)c * lda + rR + i] = R22buf[(size_t)c * D + i];
-    if (c < D && threadIdx.x == 0) A[(size_t)c * lda + rL + c] = tsqrt(*lam) * dbg_scale;
+    if (c < D && threadIdx.x == 0) A[(size_t)c * lda + rL + c] = tsqrt(*lam);
 }
 // R22 and the head of the transformed right-hand side out of a factored matrix (its first D rows), conditional on the step control
 template <typename T>
@@ -917,20 +916,8 @@ __global__ __launch_bounds__(256) void k_copy_r22(int D, const T *__restrict__ A
     for (int i = threadIdx.x; i < D; i += 256) R22buf[(size_t)c * D + i] = i <= top ? A[(size_t)c * lda + i] : (T)0;
 }
 
-// diagnostic (BA_DBG_ATB): out[c] = sum_r A[r][c] A[r][D] over the first `rows` rows -- A^T b of a built matrix, before it is factored
-template <typename T>
-__global__ __launch_bounds__(256) void k_dbg_atb(int rows, int D, const T *__restrict__ A, size_t lda, T *__restrict__ out)
-{
-    __shared__ T red[4];
-    const int c = blockIdx.x;
-    T a = 0;
-    for (int r = threadIdx.x; r < rows; r += 256) a += A[(size_t)c * lda + r] * A[(size_t)D * lda + r];
-    a = block_reduce<T, false>(a, red);
-    if (threadIdx.x == 0) out[c] = a;
-}
-
 // diagnostic (BA_DBG_QRCHECK): the self-check of a least-squares solve  min || A y - b ||  on a copy of the matrix kept from before its
-// factorisation: r = b - A y (thread per row), then out[c] = A(:, c)^T r and out[D + c] = A(:, c)^T b  (k_dbg_atb's layout, two passes)
+// factorisation: r = b - A y (thread per row), then out[c] = A(:, c)^T r and out[D + c] = A(:, c)^T b  (two passes)
 template <typename T>
 __global__ __launch_bounds__(256) void k_dbg_resid(int rows, int D, const T *__restrict__ A, size_t lda, const T *__restrict__ y, T *__restrict__ r)
 {
@@ -1016,14 +1003,10 @@ __device__ __forceinline__ void ba_bufload3(__amdgpu_buffer_rsrc_t r, unsigned o
     x1 = ba_bufload(r, off + 4, (const float *)nullptr);
     x2 = ba_bufload(r, off + 8, (const float *)nullptr);
 }
-// KO (knock-out experiment only, BA_SCHUR_KNOCKOUT=1|2: wrong results, the time tells): 1 = every ROW record is read from the first 1024
-// records (always cache-resident), 2 = every COLUMN record, 3 = both -- what an order of the work that read that side once per camera could save at most.
-// GB: groups of four entries per batch = what one memory round trip brings in per wavefront (two batches in flight).  The kernel is
-// LATENCY-bound, not traffic-bound -- round 4's knock-outs at config 5: every record gather served from cache, 2.19 -> 1.71 ms -- so
-// where the grid runs two workgroups per CU (records beyond the Infinity Cache: 256 registers per wavefront are there) the batches
-// are twice or four times as deep.
-template <typename T, bool SCALED /* dinv != 1: CHOLESKY */, int KO = 0, int GB = 2>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GB == 2 ? 4 : 1))) void k_schur_pairs(const int *__restrict__ wave_ptr, int nband, const int4 *__restrict__ chunk_info,
+// The kernel is LATENCY-bound, not traffic-bound -- round 4's knock-outs at config 5: every record gather served from cache, 2.19 -> 1.71 ms.
+// Deeper batches (four or eight groups, one wavefront per SIMD) measured slower at configs 4 and 5 (profiles/EXPERIMENTS.md 4).
+template <typename T, bool SCALED /* dinv != 1: CHOLESKY */>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_schur_pairs(const int *__restrict__ wave_ptr, int nband, const int4 *__restrict__ chunk_info,
                                                      const int2 *__restrict__ ent, const T *__restrict__ rec, unsigned rec_bytes,
                                                      const T *__restrict__ tvec, int Ml, T *__restrict__ slab, const T *__restrict__ V,
                                                      const T *__restrict__ gc, int D, int ld, T *__restrict__ S)
@@ -1058,7 +1041,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GB == 2 ? 4
         acc_t acc;
 #pragma unroll
         for (int v = 0; v < 4; v++) acc[v] = 0;
-        // (GB groups of four entries per batch: template parameter)
+        constexpr int GB = 2; // groups of four entries per batch = what one memory round trip brings in per wavefront (two batches in flight)
         struct batch_t { T a[3 * GB], d[3 * GB], b[3 * GB]; };
         auto fetch = [&](int t0, batch_t &o) { // operands of the entries 4 t0 .. 4 (t0 + GB) - 1: lane (i, k) takes entry k of each group
 #pragma unroll
@@ -1068,21 +1051,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GB == 2 ? 4
                 const int es = ok ? e : n - 1;
                 const int ia = __shfl(ia_l, es, 64), ibr = __shfl(ib_l, es, 64);
                 const bool self = ibr < 0; // self entry: the column observation is the row observation, ibr = ~point
-                const unsigned ra = (unsigned)((KO & 1) ? (ia & 1023) : ia) * RB, rb = (unsigned)((KO & 2) ? ((self ? ia : ibr) & 1023) : (self ? ia : ibr)) * RB;
+                const unsigned ra = (unsigned)ia * RB, rb = (unsigned)(self ? ia : ibr) * RB;
                 const unsigned oa = (ok && la) ? ra + lane_off : OOB, ob = (ok && la) ? rb + lane_off : OOB;
                 const unsigned od = (ok && la) ? ra + BA_REC_DINV * SZ : OOB;
-#ifdef BA_SCHUR_NARROW_LOADS
-#pragma unroll
-                for (int m = 0; m < 3; m++) {
-                    o.a[3 * u + m] = ba_bufload(rsrc, oa + m * SZ, (const T *)nullptr);
-                    if (SCALED) o.d[3 * u + m] = ba_bufload(rsrc, od + m * SZ, (const T *)nullptr);
-                    o.b[3 * u + m] = ba_bufload(rsrc, ob + m * SZ, (const T *)nullptr);
-                }
-#else
                 ba_bufload3(rsrc, oa, o.a[3 * u], o.a[3 * u + 1], o.a[3 * u + 2]);
                 if (SCALED) ba_bufload3(rsrc, od, o.d[3 * u], o.d[3 * u + 1], o.d[3 * u + 2]);
                 ba_bufload3(rsrc, ob, o.b[3 * u], o.b[3 * u + 1], o.b[3 * u + 2]);
-#endif
                 if (diag && i == 9 && ok && self) { // column 9 of B: t of the point (reduced rhs)
 #pragma unroll
                     for (int m = 0; m < 3; m++) o.b[3 * u + m] = tvec[(size_t)m * Ml + (~ibr)];

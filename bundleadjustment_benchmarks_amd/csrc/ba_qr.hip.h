@@ -169,7 +169,6 @@ template <typename T> __device__ __forceinline__ void ba_qr_tile_from_lds(const 
 // (BA_QR_HW_SQRT=1, diagnostic: the bare v_sqrt_f32 for beta -- round 3 saw config 3 accept no step with it; round 4's look at
 // that is in profiles/EXPERIMENTS.md 6.3)
 __device__ int ba_qr_hw_sqrt_flag = 0;
-__device__ int ba_qr_dbg_flag = 0; // diagnostic bits (BA_QR_DBG): 1 = full barrier in the step loop, 2 = agent acquire before the T factor re-reads V, 4 = one wave reduction per column, 8 = the column retired in front of the step's barrier
 // (x is a normal float here: smaller squared norms were rescaled by the caller.)  hw = 0: v_sqrt_f32 (1 ulp) + one Newton step;
 // 1: the bare instruction; 2: sqrtf (IEEE: ~40 dependent instructions, 280 cycles of every reflector step by the in-kernel stamps).
 __device__ __forceinline__ float ba_qr_sqrt(float x, int hw)
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(64 * BA_QR_CWV) void k_qr_chunk(T *__restrict__ A, 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = blockIdx.x;
     const int nsb = min(NSB, nsb_total - g * NSB), rows = BA_QR_PB * nsb;
     if (threadIdx.x < BA_QR_PB) taus[threadIdx.x] = (T)0;
-    const int hw_sqrt = ba_qr_hw_sqrt_flag, dbg_bits = ba_qr_dbg_flag; // (read ONCE: a load of a global per reflector step sits on the panel's critical path)
+    const int hw_sqrt = ba_qr_hw_sqrt_flag; // (read ONCE: a load of a global per reflector step sits on the panel's critical path)
 #ifdef BA_QR_STAMP
     if (nch == 1 && threadIdx.x == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); ba_qr_stamp[36] = (long long)t_; }
 #endif
@@ -353,11 +352,7 @@ __global__ __launch_bounds__(64 * BA_QR_CWV) void k_qr_chunk(T *__restrict__ A, 
             T pv[4];
 #pragma unroll
             for (int q = 0; q < CW; q++) pv[q] = q >= q0 ? pd[q] : (T)0;
-            if (dbg_bits & 4) { // (diagnostic: one reduction per column, as before round 4)
-#pragma unroll
-                for (int q = 0; q < CW; q++) pv[q] = ba_wave_sum_all<T>(pv[q]);
-            } else
-                ba_wave_sum4_all<T>(pv, lane); // the dot products of all live columns in one batched wave reduction
+            ba_wave_sum4_all<T>(pv, lane); // the dot products of all live columns in one batched wave reduction
 #pragma unroll
             for (int q = q0; q < CW; q++) pd[q] = tj * pv[q];
         }
@@ -385,16 +380,15 @@ __global__ __launch_bounds__(64 * BA_QR_CWV) void k_qr_chunk(T *__restrict__ A, 
 #ifdef BA_QR_STAMP2
             fine_now = nch == 1 && j == 8 && (wv == 0 || wv == 5); // wave 0 owns column 8 (form), wave 5 updates three columns
 #endif
-            if (jw == wv) { form(jq, j); if (dbg_bits & 8) retire(j); } // (wave-uniform) this wave's column jq is column j
+            if (jw == wv) form(jq, j); // (wave-uniform) this wave's column jq is column j
             // LDS-only barrier: the hand-over goes through LDS; __syncthreads() would also wait for the owner's global stores of the
             // retired column
-            if (dbg_bits & 1) __syncthreads();
-            else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #ifdef BA_QR_STAMP
             long long t_exit = 0;
             if (nch == 1) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); t_exit = (long long)t_; if (threadIdx.x == 0) ba_qr_stamp[j] = t_exit; }
 #endif
-            if (jw == wv && !(dbg_bits & 8)) retire(j);
+            if (jw == wv) retire(j);
 #ifdef BA_QR_STAMP2
             if (wv != 5) fine_now = false;
 #endif
@@ -416,7 +410,6 @@ __global__ __launch_bounds__(64 * BA_QR_CWV) void k_qr_chunk(T *__restrict__ A, 
 #endif
     // ---- T factor.  The retired columns are in memory (written by different waves of this workgroup: visible behind the barrier).
     __syncthreads();
-    if (dbg_bits & 2) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); __syncthreads(); }
     {
         typedef typename ba_acc<T>::type acc_t;
         const int i = lane & 15, q = lane >> 4;
@@ -716,9 +709,7 @@ __global__ __launch_bounds__(256) void k_qr_backsolve(const T *__restrict__ A, s
 // st2 != nullptr (with two events): the trailing updates run on st2 beside the panel's chunk chain -- level L + 1 of the chain only
 // needs the panel's own R's from level L, not the trailing update of level L -- and the next panel waits for the last of them
 // (fork / join by events: also valid inside a stream capture).  6.2 -> 5.3 ms per trial at config 3 in round 2.  Look-ahead (every
-// level's reflectors to the next panel's 32 columns first, so that the next chain starts before the rest is done): on `st` itself it
-// cost more than it gave in round 2 (5.7 ms: five more launches on the critical stream); round 3 puts those launches on a THIRD
-// stream -- the chain stream carries nothing but the chunk kernels (ba_qr_side).
+// level's reflectors to the next panel's 32 columns first) was slower, on `st` and on a third stream alike (profiles/EXPERIMENTS.md 6.2).
 // ---- sharded QRKIT: distributed TSQR ----------------------------------------------------------------------------------------------
 // Every shard factors the rows of J2bot it owns (ba_qr_factor); what it contributes to the whole matrix's factor is its D x D
 // triangle R_r and the head of Q_r^T rhs.  k_qr_stack_pack copies both into block r of a zeroed (world D) x (D + 1) matrix, behind
@@ -751,26 +742,21 @@ template <typename T> inline void ba_qr_backsolve(hipStream_t st, const T *A, si
     hipLaunchKernelGGL((k_qr_backsolve<T>), dim3(1), dim3(256), sizeof(T) * (size_t)(D + 64 + 64 * 64), st, A, lda, D, y);
 }
 
-// Side streams of the factorisation (all nullptr: everything on `st`).  st2 alone: the trailing updates beside the chunk chain.
-// st2 + st3 (look-ahead): a level's reflectors go to the NEXT panel's 32 columns on st3 and to the rest on st2; the next chain
-// waits for st3 only.
+// Side stream of the factorisation (all nullptr: everything on `st`): the trailing updates on st2 beside the chunk chain.
 #define BA_QR_TAU_LEVELS 8 /* TSQR levels the T storage has room for (16^8 chunks) */
 struct ba_qr_side {
-    hipStream_t st2 = nullptr, st3 = nullptr;
-    hipEvent_t ev_chunk = nullptr, ev_apply = nullptr, ev_next = nullptr; // chunk done (st) | rest updated (st2) | next panel updated (st3)
+    hipStream_t st2 = nullptr;
+    hipEvent_t ev_chunk = nullptr, ev_apply = nullptr; // chunk done (st) | trailing columns updated (st2)
     const int *go = nullptr; // every kernel of the factorisation returns at once while *go == 0 (MOREQR's outer QR behind a rejected trial)
     bool two() const { return st2 && ev_chunk && ev_apply; }
-    bool lookahead() const { return two() && st3 && ev_next; }
 };
 
 template <typename T>
-inline void ba_qr_factor(hipStream_t st, T *A, size_t lda, int mrows, int D, T *tau_all, size_t tau_level_stride, const ba_qr_side &sd = ba_qr_side())
+inline void ba_qr_factor(hipStream_t st, T *A, size_t lda, int mrows, int D, T *tau, size_t tau_level_stride, const ba_qr_side &sd = ba_qr_side())
 {
-    // tau_all: BA_QR_TAU_LEVELS level slots of tau_level_stride scalars, TWICE with look-ahead: the chain of panel p + 1 writes its T
-    // factors while st2 still applies panel p's
+    // tau: BA_QR_TAU_LEVELS level slots of tau_level_stride scalars
     constexpr int NSB1 = ba_qr_cfg<T>::NSB, NSBU = ba_qr_cfg<T>::NSBU;
-    const bool two = sd.two(), la = sd.lookahead();
-    bool rest_pending = false, next_pending = false; // st2 / st3 hold updates that `st` (or the other one) has not waited for yet
+    const bool two = sd.two();
     auto apply = [&](hipStream_t sa, int level, int nch, int nsb, long long stride, const T *tl, int c0, int bw, int col0, int col1) {
         const int nct = (col1 - col0 + BA_QR_PB - 1) / BA_QR_PB; // strips of 32 columns
         // (8 x ceil(nch / 8) x nct workgroups: chunk g's strips sit at blockIdx % 8 == g % 8)
@@ -780,21 +766,11 @@ inline void ba_qr_factor(hipStream_t st, T *A, size_t lda, int mrows, int D, T *
         else
             hipLaunchKernelGGL((k_qr_apply<T, NSBU>), ga, dim3(64 * BA_QR_AW), 0, sa, A, lda, c0, bw, c0, level, stride, nsb, tl, col0, col1, nch, nct, sd.go);
     };
-    const char *stop_env = getenv("BA_QR_STOP_PANEL"); // diagnostic: leave the factorisation behind this panel (its T factors stay in tau_all)
-    const int stop_panel = stop_env ? atoi(stop_env) : -1;
     for (int c0 = 0; c0 < D; c0 += BA_QR_PB) {
-        if (stop_panel >= 0 && c0 / BA_QR_PB > stop_panel) break;
         const int bw = D - c0 < BA_QR_PB ? D - c0 : BA_QR_PB;
         const int col0 = c0 + bw, col1 = D + 1; // trailing columns incl. the right-hand side
-        const int colm = la ? (col0 + BA_QR_PB < col1 ? col0 + BA_QR_PB : col1) : col0; // look-ahead: [col0, colm) is the next panel
         int nsb = (mrows - c0 + BA_QR_PB - 1) / BA_QR_PB; // 32-row blocks from the panel's first row down
         long long stride = BA_QR_PB;
-        T *tau = tau_all + (la && ((c0 / BA_QR_PB) & 1) ? (size_t)BA_QR_TAU_LEVELS * tau_level_stride : 0);
-        if (next_pending) { // this panel's columns carry every earlier reflector once st3 is done with them
-            (void)hipStreamWaitEvent(st, sd.ev_next, 0);
-            next_pending = false;
-        }
-        bool first_next = true;
         for (int level = 1;; level++) {
             const int fan = level == 1 ? NSB1 : NSBU;
             const int nch = (nsb + fan - 1) / fan;
@@ -802,37 +778,21 @@ inline void ba_qr_factor(hipStream_t st, T *A, size_t lda, int mrows, int D, T *
             if (level == 1) hipLaunchKernelGGL((k_qr_chunk<T, NSB1>), dim3(nch), dim3(64 * BA_QR_CWV), 0, st, A, lda, c0, bw, c0, level, stride, nsb, tl, nch, sd.go);
             else hipLaunchKernelGGL((k_qr_chunk<T, NSBU>), dim3(nch), dim3(64 * BA_QR_CWV), 0, st, A, lda, c0, bw, c0, level, stride, nsb, tl, nch, sd.go);
             if (col0 < col1) {
-                if (two) (void)hipEventRecord(sd.ev_chunk, st);
-                if (la) {
-                    (void)hipStreamWaitEvent(sd.st3, sd.ev_chunk, 0);
-                    if (first_next && rest_pending) (void)hipStreamWaitEvent(sd.st3, sd.ev_apply, 0); // the previous panels' reflectors come first
-                    first_next = false;
-                    apply(sd.st3, level, nch, nsb, stride, (const T *)tl, c0, bw, col0, colm);
+                if (two) {
+                    (void)hipEventRecord(sd.ev_chunk, st);
+                    (void)hipStreamWaitEvent(sd.st2, sd.ev_chunk, 0);
                 }
-                if (colm < col1) {
-                    if (two) (void)hipStreamWaitEvent(sd.st2, sd.ev_chunk, 0);
-                    apply(two ? sd.st2 : st, level, nch, nsb, stride, (const T *)tl, c0, bw, colm, col1);
-                }
+                apply(two ? sd.st2 : st, level, nch, nsb, stride, (const T *)tl, c0, bw, col0, col1);
             }
             if (nch == 1) break;
             nsb = nch;
             stride *= fan;
         }
-        if (two && colm < col1) {
+        if (two && col0 < col1) { // the next panel (and the back substitution) read what the trailing updates wrote
             (void)hipEventRecord(sd.ev_apply, sd.st2);
-            rest_pending = true;
-            if (!la) { // the next panel (and the back substitution) read what the trailing updates wrote
-                (void)hipStreamWaitEvent(st, sd.ev_apply, 0);
-                rest_pending = false;
-            }
-        }
-        if (la && col0 < col1) {
-            (void)hipEventRecord(sd.ev_next, sd.st3);
-            next_pending = true;
+            (void)hipStreamWaitEvent(st, sd.ev_apply, 0);
         }
     }
-    if (next_pending) (void)hipStreamWaitEvent(st, sd.ev_next, 0);
-    if (rest_pending) (void)hipStreamWaitEvent(st, sd.ev_apply, 0);
 }
 
 template <typename T>

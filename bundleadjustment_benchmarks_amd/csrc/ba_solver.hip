@@ -129,7 +129,7 @@ template <typename T> struct Solver final : SolverBase {
     int schur_window = 0;
     int nred = 0;
     const bool no_fold = getenv("BA_NO_FOLD") != nullptr; // dev switch: every launch of its own again (A/B timing on one box)
-    int schur_grid = 1, schur_wgs = 4 /* workgroups of k_schur_pairs per CU */, schur_bands = 8, schur_nband = 1, schur_gb = 2 /* groups of four entries per batch */;
+    int schur_grid = 1, schur_wgs = 4 /* workgroups of k_schur_pairs per CU */, schur_bands = 8, schur_nband = 1;
     // state: x = d_cam[0], d_pts[0]; xTest = d_cam[1], d_pts[1] (x = xTest is a device-side copy, k_commit)
     // linearisation at x (r, J, J^T r, block diagonals, MOREQR's outer factors): one set
     DevBuf<T> d_r, d_Jc, d_Jp, d_JcA, d_U0, d_gp, d_V, d_gc, d_rec0, d_dinv0, d_tvec0, d_tri0;
@@ -140,12 +140,11 @@ template <typename T> struct Solver final : SolverBase {
     DevBuf<T> d_qA, d_qtau, d_q1obs, d_q1lam;
     size_t q_lda = 0, q_tau_stride = 0;
     hipStream_t st_qr = nullptr;   // second stream of the dense QR: trailing updates beside the panel's chunk chain (ba_qr_solve)
-    hipStream_t st_qr3 = nullptr;  // third one: the look-ahead updates (the next panel's columns)
-    hipEvent_t ev_qr[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_qr[2] = {nullptr, nullptr};
     ba_qr_side qr_side() const
     {
         ba_qr_side sd;
-        sd.st2 = st_qr; sd.st3 = st_qr3; sd.ev_chunk = ev_qr[0]; sd.ev_apply = ev_qr[1]; sd.ev_next = ev_qr[2];
+        sd.st2 = st_qr; sd.ev_chunk = ev_qr[0]; sd.ev_apply = ev_qr[1];
         return sd;
     }
     int q_rows = 0;
@@ -158,7 +157,6 @@ template <typename T> struct Solver final : SolverBase {
     bool more_qr_on = true;
     bool dense_qr() const { return kind == BA_QRKIT || kind == BA_QRSPQR || more_qr(); }
     bool more_qr() const { return kind == BA_MOREQR && more_qr_on; }
-    DevBuf<T> d_dbg; // diagnostic buffer (BA_DBG_ATB)
     DevBuf<T> d_mQl, d_mQR, d_R22; // MOREQR: the inner point blocks' thin Q (lambda rows, R1 rows: [Ml][9] each); R22 | c2 of the outer QR, D x (D + 1)
     int outer_rows() const { return 2 * Kl + 3 * Ml + D; }               // J2bot (QRKIT / QRSPQR per trial; MOREQR per outer iteration, lambda = 0)
     int inner_rows() const { return more_qr() ? 6 * Ml + 2 * D : outer_rows(); } // the matrix a TRIAL factors
@@ -210,7 +208,6 @@ template <typename T> struct Solver final : SolverBase {
         if (comm) ba_rccl_destroy(comm);
         if (own_stream && st) (void)hipStreamDestroy(st);
         if (st_qr) (void)hipStreamDestroy(st_qr);
-        if (st_qr3) (void)hipStreamDestroy(st_qr3);
         for (hipEvent_t e : ev_qr) if (e) (void)hipEventDestroy(e);
     }
 
@@ -274,7 +271,6 @@ template <typename T> struct Solver final : SolverBase {
             // memory, and fewer wavefronts in flight walking the pair list side by side leave more of a row camera's records in the
             // L2 (2.23 -> 2.07 ms at config 5; nothing either way at config 4, whose 58 MB of records stay in the Infinity Cache).
             if ((unsigned long long)Kl * BA_REC * sizeof(T) > (256ull << 20)) { schur_wgs = 2; schur_window = 1; }
-            if (const char *ev = getenv("BA_SCHUR_GB")) schur_gb = atoi(ev); // (A/B only: deeper batches measured SLOWER at configs 4 and 5, profiles/EXPERIMENTS.md 4)
             if (const char *ev = getenv("BA_SCHUR_WGS")) schur_wgs = std::max(1, std::min(8, atoi(ev)));
             if (const char *ev = getenv("BA_SCHUR_BANDS")) schur_bands = atoi(ev);
             // Chunks dealt to the wavefronts of the persistent pair kernel, longest first, always to the least loaded wavefront
@@ -284,8 +280,8 @@ template <typename T> struct Solver final : SolverBase {
             {
                 // every wavefront of the persistent grid must be resident at once (the dealing assumes they run side by side)
                 int nb = 0;
-                const hipError_t oe = kind == BA_CHOLESKY ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_schur_pairs<T, true, 0, 2>, 256, 0)
-                                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_schur_pairs<T, false, 0, 2>, 256, 0);
+                const hipError_t oe = kind == BA_CHOLESKY ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_schur_pairs<T, true>, 256, 0)
+                                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_schur_pairs<T, false>, 256, 0);
                 if (oe == hipSuccess && nb >= 1) schur_wgs = std::min(schur_wgs, nb);
             }
             schur_grid = std::max(1, std::min((sx.nchunks + 3) / 4, schur_wgs * num_cus));
@@ -389,28 +385,23 @@ template <typename T> struct Solver final : SolverBase {
         if ((rc = d_lm.alloc(1))) return rc;
         if ((rc = d_pperm.upload(std::vector<int>(M1, 0 | (1 << 2) | (2 << 4))))) return rc; // identity (CHOLESKY never pivots)
         if (dense_qr()) {
-            if (const char *ev = getenv("BA_QR_DBG")) { // diagnostic bits (ba_qr.hip.h: ba_qr_dbg_flag)
-                const int bits = atoi(ev);
-                HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(ba_qr_dbg_flag), &bits, sizeof(int)));
-            }
-            if (const char *ev = getenv("BA_QR_HW_SQRT")) { // diagnostic switch (ba_qr.hip.h: ba_qr_sqrt)
-                const int on = atoi(ev); // 0 (default): v_sqrt_f32 + one Newton step, 1: the bare instruction, 2: sqrtf
+            {
+                // diagnostic switch BA_QR_HW_SQRT (ba_qr.hip.h: ba_qr_sqrt), written at every creation: the flag is process-global
+                const char *ev = getenv("BA_QR_HW_SQRT");
+                const int on = ev ? atoi(ev) : 0; // 0 (default): v_sqrt_f32 + one Newton step, 1: the bare instruction, 2: sqrtf
                 HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(ba_qr_hw_sqrt_flag), &on, sizeof(int)));
             }
             // J2bot is dense: (2K + 3M + D) x (D + 1) scalars (config 3: 256 MB in fp32; a problem whose J2bot does not fit is refused)
             // (a camera may see a point more than once: k_qrkit_build / k_more_build add such observations' blocks up -- rounds 2 - 3 refused them)
             q_rows = std::max(outer_rows(), inner_rows());
-            if (more_qr()) { AL(d_mQl, 9 * M1); AL(d_mQR, 9 * M1); AL(d_R22, (size_t)D * (D + 1)); AL(d_dbg, (size_t)D); }
+            if (more_qr()) { AL(d_mQl, 9 * M1); AL(d_mQR, 9 * M1); AL(d_R22, (size_t)D * (D + 1)); }
             if (!getenv("BA_QR_ONE_STREAM")) {
                 HIPCHK(hipStreamCreateWithFlags(&st_qr, hipStreamNonBlocking));
-                // (look-ahead on a third stream: measured, not the default -- 2.27 - 2.34 against 2.38 ms stand-alone, but 375 against
-                // 418 LM it/s inside the captured iteration graph, profiles/EXPERIMENTS.md 6.2)
-                if (getenv("BA_QR_LOOKAHEAD")) HIPCHK(hipStreamCreateWithFlags(&st_qr3, hipStreamNonBlocking));
                 for (auto &e : ev_qr) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             }
             q_lda = (size_t)q_rows + 64;
             q_tau_stride = (size_t)((std::max(q_rows, world * D) + ba_qr_cfg<T>::CH - 1) / ba_qr_cfg<T>::CH + 2) * BA_QR_PB * BA_QR_PB; // a 32 x 32 T factor per chunk (of J2bot's rows or, sharded, of the stack's)
-            AL(d_qA, q_lda * (size_t)(D + 1)); AL(d_qtau, (st_qr3 ? 2 : 1) * BA_QR_TAU_LEVELS * q_tau_stride); AL(d_q1obs, 6 * K1); AL(d_q1lam, 9 * M1);
+            AL(d_qA, q_lda * (size_t)(D + 1)); AL(d_qtau, BA_QR_TAU_LEVELS * q_tau_stride); AL(d_q1obs, 6 * K1); AL(d_q1lam, 9 * M1);
             if (world > 1) AL(d_qB, qb_count());
         }
         AL(d_gcg, (size_t)D); AL(d_dslab, (size_t)BA_SLAB * (sx.ndchunks > 0 ? sx.ndchunks : 1));
@@ -632,16 +623,10 @@ template <typename T> struct Solver final : SolverBase {
         if (sx.nchunks > 0) {
             // persistent: schur_wgs workgroups per CU, every wavefront walks its own balanced list of chunks (see k_schur_pairs)
             const dim3 gp(schur_grid);
-#define BA_PAIRS(SC, KO_, GB_) hipLaunchKernelGGL((k_schur_pairs<T, SC, KO_, GB_>), gp, dim3(256), 0, st, d_wave_ptr.p, schur_nband, d_chunk_info.p, d_ent.p, d_rec.p, \
+#define BA_PAIRS(SC) hipLaunchKernelGGL((k_schur_pairs<T, SC>), gp, dim3(256), 0, st, d_wave_ptr.p, schur_nband, d_chunk_info.p, d_ent.p, d_rec.p, \
                                                   (unsigned)(sizeof(T) * d_rec.n), d_tvec.p, Ml, d_slab.p, d_V.p, d_gc.p, D, ld, d_S.p)
             // SCALED: CHOLESKY is the only symbol whose point blocks carry a diagonal D (dinv != 1)
-            static const int ko = getenv("BA_SCHUR_KNOCKOUT") ? atoi(getenv("BA_SCHUR_KNOCKOUT")) : 0; // (experiment: wrong results, see k_schur_pairs)
-            if (ko == 1) BA_PAIRS(false, 1, 2);
-            else if (ko == 2) BA_PAIRS(false, 2, 2);
-            else if (ko == 3) BA_PAIRS(false, 3, 2);
-            else if (schur_gb == 8) { if (kind == BA_CHOLESKY) BA_PAIRS(true, 0, 8); else BA_PAIRS(false, 0, 8); }
-            else if (schur_gb == 4) { if (kind == BA_CHOLESKY) BA_PAIRS(true, 0, 4); else BA_PAIRS(false, 0, 4); }
-            else if (kind == BA_CHOLESKY) BA_PAIRS(true, 0, 2); else BA_PAIRS(false, 0, 2);
+            if (kind == BA_CHOLESKY) BA_PAIRS(true); else BA_PAIRS(false);
 #undef BA_PAIRS
         }
         const int post_blocks = lamf ? (Dp + 2) / 3 : 0;
@@ -749,12 +734,7 @@ template <typename T> struct Solver final : SolverBase {
         if (Kl > 0)
             hipLaunchKernelGGL((k_more_build<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, D, d_obs_cam.p, d_obs_pt.p, d_pt_ptr.p, d_rec0.p, d_rec.p, d_mQl.p, d_mQR.p,
                                d_tvec0.p, d_tvec.p, d_qA.p, q_lda);
-        static const double dbg = getenv("BA_DBG_TAIL") ? (atof(getenv("BA_DBG_TAIL")) == -1.0 ? -1.0 : 1.0 + atof(getenv("BA_DBG_TAIL"))) : 1.0;
-        if (rank == 0) hipLaunchKernelGGL((k_more_tail<T>), dim3(D + 1), dim3(256), 0, st, Ml, D, d_R22.p, d_scal.p + SC_LAMBDA, d_qA.p, q_lda, (T)dbg);
-        static const bool dbg_atb = getenv("BA_DBG_ATB") != nullptr;
-        if (dbg_atb) { // A^T b of the matrix as built, into the spare half of the step vector (getter 13)
-            hipLaunchKernelGGL((k_dbg_atb<T>), dim3(D), dim3(256), 0, st, inner_rows(), D, (const T *)d_qA.p, q_lda, d_dbg.p);
-        }
+        if (rank == 0) hipLaunchKernelGGL((k_more_tail<T>), dim3(D + 1), dim3(256), 0, st, Ml, D, d_R22.p, d_scal.p + SC_LAMBDA, d_qA.p, q_lda);
     }
     // MOREQR per outer iteration (behind k_elim_qr with lambda = 0; BacktrackLevMarqMore.h:288-291): the dense QR of J2bot(lambda = 0).
     // Part 1 (capturable): build + this shard's factorisation (+ sharded: its R | c2 into the zeroed stack).  Part 2: sharded -- the
@@ -1128,14 +1108,6 @@ template <typename T> struct Solver final : SolverBase {
             int rcg;
             if ((rcg = dl(d_qtau.p, n, hh))) return rcg;
             for (size_t c = 0; c < n; c++) out[c] = (double)hh[c];
-            return BA_OK;
-        }
-        case 13: { // diagnostic (BA_DBG_ATB): A^T b of MOREQR's inner matrix as built
-            if (!more_qr() || n != (size_t)D) return BA_ERR_ARG;
-            std::vector<T> hh;
-            int rcg;
-            if ((rcg = dl(d_dbg.p, (size_t)D, hh))) return rcg;
-            for (int c = 0; c < D; c++) out[c] = (double)hh[c];
             return BA_OK;
         }
         case 12: { // diagnostic: the first D rows of the factored matrix, all D + 1 columns (R | the head of Q^T rhs), column-major D x (D + 1)

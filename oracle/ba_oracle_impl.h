@@ -660,9 +660,9 @@ static void FN(more_trial)(int M, const int *pt_ptr, S lambda, const FN(more_t) 
  * oracle's rounding noise decides where its free run stops. */
 static int ora_wide_sums_flag = 0;
 void ora_set_wide_sums(int on) { ora_wide_sums_flag = on; }
-/* MOREQR's right block QR only (solve_more_qr) instead of the LDL^T of S = (Jc'Jc + lambda I) - sum Z Z': off by default, like the
- * product's BA_MOREQR_QR switch (round 4: the route exists on both sides and agrees to 1e-7 / 1e-10 on the first step; the product's
- * dense QR kernels have a sporadic accuracy defect that keeps it from being the default). */
+/* MOREQR's right block QR only (solve_more_qr) instead of the LDL^T of S = (Jc'Jc + lambda I) - sum Z Z': on by default, like the
+ * product's BA_MOREQR_QR switch (the route exists on both sides and agrees to 1e-7 / 1e-10 on the first step; 0 selects the LDL^T
+ * form, which the tests keep covering). */
 static int ora_more_qr_flag = 1; /* MOREQR: QR-only right block (the reference's route); 0 = LDL^T of the same reduced system */
 void ora_set_more_qr(int on) { ora_more_qr_flag = on; }
 #endif

@@ -128,7 +128,7 @@ template <typename T> struct Solver final : SolverBase {
     DevBuf<int> d_red_pairs;   // pairs k_schur_reduce writes: those without entries and those with several chunks
     int schur_window = 0;
     int nred = 0;
-    const bool no_fold = getenv("BA_NO_FOLD") != nullptr; // dev switch: every launch of its own again (A/B timing on one box)
+    bool no_fold = false; // BA_NO_FOLD (dev switch): every launch of its own again (A/B timing on one box)
     int schur_grid = 1, schur_wgs = 4 /* workgroups of k_schur_pairs per CU */, schur_bands = 8, schur_nband = 1;
     // state: x = d_cam[0], d_pts[0]; xTest = d_cam[1], d_pts[1] (x = xTest is a device-side copy, k_commit)
     // linearisation at x (r, J, J^T r, block diagonals, MOREQR's outer factors): one set
@@ -184,6 +184,7 @@ template <typename T> struct Solver final : SolverBase {
     bool fuse = false;
     DevBuf<int> d_eb;
     bool have_step = false;
+    bool step_level = false; // inside try_step: the segments add the phase events, the kept S, the QR self-check and their own test-energy sum
     int num_cus = 256; // of the device the solver lives on
     double wall_khz = 1e5;
     // A hand-off between workgroups of one launch that timed out (device error word) is survivable: the trial is repeated with the
@@ -250,6 +251,8 @@ template <typename T> struct Solver final : SolverBase {
         memset((void *)h_log, 0, sizeof(ba_lm_host));
         HIPCHK(hipHostGetDevicePointer((void **)&d_log, (void *)h_log, 0));
         use_graph = getenv("BA_NO_GRAPH") == nullptr;
+        no_fold = getenv("BA_NO_FOLD") != nullptr;
+        dbg_qrcheck = getenv("BA_DBG_QRCHECK") != nullptr;
         dist_factor = getenv("BA_DIST_FACTOR") != nullptr && atoi(getenv("BA_DIST_FACTOR")) != 0;
         if (const char *wd = getenv("BA_WATCHDOG_S")) { const double v = atof(wd); if (v > 0) watchdog_s = v; }
         {
@@ -771,15 +774,12 @@ template <typename T> struct Solver final : SolverBase {
             hipLaunchKernelGGL((k_copy_r22<T>), dim3(D + 1), dim3(256), 0, st, D, (const T *)d_qA.p, q_lda, d_R22.p, go);
         return BA_OK;
     }
-    DevBuf<T> d_qAcopy, d_dbgr, d_dbg2; // BA_DBG_QRCHECK
+    bool dbg_qrcheck = false; // BA_DBG_QRCHECK
+    DevBuf<T> d_qAcopy, d_dbgr, d_dbg2;
     void launch_qrkit_solve()
     {
-        // BA_DBG_QRCHECK (diagnostic, step-level seam only): a copy of the matrix, and behind the solve its normal-equation residual (getter 14)
-        bool chk = getenv("BA_DBG_QRCHECK") != nullptr;
-        if (chk) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            chk = hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
-        }
+        // BA_DBG_QRCHECK (diagnostic, step-level calls only): a copy of the matrix, and behind the solve its normal-equation residual (getter 14)
+        const bool chk = dbg_qrcheck && step_level;
         if (chk) {
             if (!d_qAcopy.p) { (void)d_qAcopy.alloc(d_qA.n); (void)d_dbgr.alloc(q_lda); (void)d_dbg2.alloc((size_t)2 * D); }
             (void)hipMemcpyAsync(d_qAcopy.p, d_qA.p, sizeof(T) * d_qA.n, hipMemcpyDeviceToDevice, st);
@@ -885,13 +885,20 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
 
-    // The segments of one trial (everything behind lambda in SC_LAMBDA).  Single shard: A + B back to back; sharded: an
-    // all-reduce of the packed system between A and B and one of the three step scalars behind B.
+    // S, or (QRKIT / QRSPQR / MOREQR) the dense J2bot
+    void launch_assemble() { if (dense_qr()) launch_qrkit_build(); else launch_schur(); }
+    // a phase boundary of try_step's timing (ba_timing); nothing in a captured segment
+    int mark(int e) { if (step_level) HIPCHK(hipEventRecord(ev[e], st)); return BA_OK; }
+    // The segments of one trial (everything behind lambda in SC_LAMBDA).  Single shard: A + B back to back; sharded: the
+    // exchange between A and B and an all-reduce of the step scalars behind B.  try_step runs the same segments (step_level).
     int launch_seg_a()
     {
+        int rc;
         launch_eliminate();
-        if (dense_qr()) { launch_qrkit_build(); return sharded() ? launch_qr_stack_pack() : BA_OK; }
-        launch_schur();
+        if ((rc = mark(EV_T1))) return rc;
+        launch_assemble();
+        if ((rc = mark(EV_T2))) return rc;
+        if (dense_qr()) return sharded() ? launch_qr_stack_pack() : BA_OK;
         if (dist_on()) return launch_dist_pack();
         return sharded() ? launch_pack(false) : BA_OK;
     }
@@ -900,16 +907,26 @@ template <typename T> struct Solver final : SolverBase {
         int rc;
         if (dist_on()) { if ((rc = launch_dist_unpack())) return rc; }
         else if (sharded() && !dense_qr() && (rc = launch_pack(true))) return rc;
+        if ((rc = mark(EV_T3))) return rc;
         if (dense_qr()) { if (sharded()) launch_qr_stack_solve(); else launch_qrkit_solve(); }
         else {
             launch_post_reduce();
-            if (dist_factor && sharded()) { if ((rc = launch_factor_solve_dist())) return rc; }
+            if (keep && step_level) {
+                if (!d_Skeep.p && (rc = d_Skeep.alloc(d_S.n))) return rc;
+                HIPCHK(hipMemcpyAsync(d_Skeep.p, d_S.p, sizeof(T) * d_S.n, hipMemcpyDeviceToDevice, st));
+            }
+            if (dist_on()) { if ((rc = launch_factor_solve_dist())) return rc; }
             else launch_factor_solve();
         }
+        if ((rc = mark(EV_T4))) return rc;
         launch_backsub_retract();
-        launch_test_energy(!ctl_reduces()); // (single shard: k_lm_control sums the three partial arrays at its head)
+        if ((rc = mark(EV_T5))) return rc;
+        launch_test_energy(step_level || !ctl_reduces()); // (single shard: k_lm_control sums the three partial arrays at its head)
         return BA_OK;
     }
+    // reduced camera system (or stack of R factors) + rhs + g_c + energy tail; the distributed factor only needs each rank's own
+    // block columns summed: a reduce-scatter (half the bytes) + g_c and the energy in a small all-reduce.  Single shard: nothing.
+    int exchange() { return dist_on() ? dist_exchange() : allreduce(xchg_ptr(), xchg_count(), 0); }
     // step control on the device, x = xTest and the linearisation of the next outer iteration, the latter two conditional
     int launch_seg_ctl()
     {
@@ -921,36 +938,16 @@ template <typename T> struct Solver final : SolverBase {
     }
 
     // m_solver.compute .. dx; xTest = x (+) dx; m_functor(xTest); rhoScale (BacktrackLevMarqQRChol.h:291-375): the step-level
-    // seam, host-synchronous, with per-phase events (ba_minimize runs the same launches as graphs under device-side control).
+    // seam, host-synchronous: the segments ba_minimize replays as graphs under device-side control, with per-phase events.
     int try_step(double lambda_d, double *e_test, double *rho_scale, double *dx_norm) override
     {
         int rc;
         if ((rc = set_lambda((T)lambda_d))) return rc;
         HIPCHK(hipEventRecord(ev[EV_T0], st));
-        launch_eliminate();
-        HIPCHK(hipEventRecord(ev[EV_T1], st));
-        if (dense_qr()) launch_qrkit_build(); else launch_schur();
-        HIPCHK(hipEventRecord(ev[EV_T2], st));
-        if (sharded()) {
-            if (dense_qr()) { if ((rc = launch_qr_stack_pack()) || (rc = allreduce(d_qB.p, qb_count(), 0))) return rc; }
-            else if (dist_on()) { if ((rc = launch_dist_pack()) || (rc = dist_exchange()) || (rc = launch_dist_unpack())) return rc; }
-            else if ((rc = launch_pack(false)) || (rc = allreduce(d_pack.p, pack_count() + 1, 0)) || (rc = launch_pack(true))) return rc;
-        }
-        HIPCHK(hipEventRecord(ev[EV_T3], st));
-        if (dense_qr()) { if (sharded()) launch_qr_stack_solve(); else launch_qrkit_solve(); }
-        else {
-            launch_post_reduce();
-            if (keep) {
-                if (!d_Skeep.p && (rc = d_Skeep.alloc(d_S.n))) return rc;
-                HIPCHK(hipMemcpyAsync(d_Skeep.p, d_S.p, sizeof(T) * d_S.n, hipMemcpyDeviceToDevice, st));
-            }
-            if (dist_factor && sharded()) { if ((rc = launch_factor_solve_dist())) return rc; }
-            else launch_factor_solve();
-        }
-        HIPCHK(hipEventRecord(ev[EV_T4], st));
-        launch_backsub_retract();
-        HIPCHK(hipEventRecord(ev[EV_T5], st));
-        launch_test_energy();
+        step_level = true;
+        if (!(rc = launch_seg_a()) && !(rc = exchange())) rc = launch_seg_b();
+        step_level = false;
+        if (rc) return rc;
         HIPCHK(hipEventRecord(ev[EV_T6], st));
         if ((rc = allreduce(d_scal.p + SC_ETEST, N_STEP_SCALARS, 0))) return rc; // (the error word too: a time-out of one shard fails the step on all)
         if ((rc = fetch_scalars())) return rc;
@@ -1207,10 +1204,7 @@ template <typename T> struct Solver final : SolverBase {
         {
             if ((rc = run_seg(&g_a, &Solver::launch_seg_a, graphs))) return rc;
             HIPCHK(hipEventRecord(e.e[1], st));
-            // reduced camera system (or stack of R factors) + rhs + g_c + energy tail; the distributed factor only needs each rank's own
-            // block columns summed: a reduce-scatter (half the bytes) + g_c and the energy in a small all-reduce
-            if (dist_on()) { if ((rc = dist_exchange())) return rc; }
-            else if ((rc = allreduce(xchg_ptr(), xchg_count(), 0))) return rc;
+            if ((rc = exchange())) return rc;
             HIPCHK(hipEventRecord(e.e[2], st));
             if ((rc = run_seg(&g_b, &Solver::launch_seg_b, graphs && !dist_on()))) return rc; // (the distributed factor's collectives sit INSIDE segment B)
             HIPCHK(hipEventRecord(e.e[3], st));
@@ -1451,12 +1445,11 @@ template <typename T> struct Solver final : SolverBase {
             case 0: launch_eval(false, 0); break;
             case 1: launch_eval(true, 0); launch_grad(); break;
             case 2: launch_eliminate(); break;
-            case 3: if (dense_qr()) launch_qrkit_build(); else launch_schur(); break; // (QRKIT: J2bot instead of S)
+            case 3: launch_assemble(); break; // (QRKIT: J2bot instead of S)
             case 4:
-                if (dense_qr()) { launch_qrkit_build(); launch_qrkit_solve(); break; }
-                launch_schur(); // the factorisation is in place: rebuild S first (timed separately by phase 3)
-                launch_post_reduce();
-                launch_factor_solve();
+                launch_assemble(); // the factorisation is in place: rebuild S first (timed separately by phase 3)
+                if (dense_qr()) launch_qrkit_solve();
+                else { launch_post_reduce(); launch_factor_solve(); }
                 break;
             case 5: launch_backsub_retract(); break;
             case 8: // the linearisation as ba_minimize runs it behind an accepted step: fused point part (+ CHOLESKY: the next trial's records)
@@ -1465,8 +1458,8 @@ template <typename T> struct Solver final : SolverBase {
                 break;
             case 6: // dense factorisation only (k_ldlt_panel + k_ldlt_step / k_ldlt_update; QRKIT: the Householder QR + solve): events around it, per rep
             case 7: // backward sweep only (k_ldlt_backflow; QRKIT: nothing, the solve is part of 6)
+                launch_assemble();
                 if (dense_qr()) {
-                    launch_qrkit_build();
                     HIPCHK(hipEventRecord(ev[EV_T2], st));
                     if (phase == 6) launch_qrkit_solve();
                     HIPCHK(hipEventRecord(ev[EV_T3], st));
@@ -1474,7 +1467,6 @@ template <typename T> struct Solver final : SolverBase {
                     acc_ms += ev_ms(EV_T2, EV_T3);
                     break;
                 }
-                launch_schur();
                 launch_post_reduce();
                 if (phase == 6) HIPCHK(hipEventRecord(ev[EV_T2], st));
                 launch_factor();

@@ -672,3 +672,20 @@ def test_dense_qr_self_check_over_lambdas(ba, gpu_ok, prob21, monkeypatch, kind_
             worst = max(worst, v)
             assert v < 1e-11, (kind_name, lam, v)
     print("\n%s: worst |A'(b - Ay)| / |A'b| over 40 solves %.2e" % (kind_name, worst))
+
+
+@pytest.mark.parametrize("kind_name", ["QRKIT", "QRCHOL", "CHOLESKY", "MOREQR"])
+def test_step_seam_runs_the_production_trial(ba, gpu_ok, prob21, monkeypatch, kind_name):
+    """try_step (the seam nearly every parity test goes through) and ba_minimize (captured graphs, what bench.py times) run one
+    trial's launches from the same sequence: the trial point xTest of the first trial -- written whether it is accepted or
+    not -- must be the same bits on both paths.  lambda0 as ba_minimize computes it from max diag J'J."""
+    import math
+    monkeypatch.delenv("BA_MOREQR_QR", raising=False)
+    kind = getattr(ba, kind_name)
+    a = ba.Solver(prob21, kind, ba.F64)
+    _, dmax = a.linearize()
+    a.try_step(1e-6 * math.sqrt(dmax) if kind == ba.MOREQR else 1e-12 * dmax)
+    b = ba.Solver(prob21, kind, ba.F64)
+    b.minimize(max_trials=1)
+    for what in (ba.GET_CAMS_TEST, ba.GET_POINTS_TEST):
+        assert np.array_equal(a.get(what), b.get(what)), (kind_name, what)

@@ -222,6 +222,125 @@ int ref_minimize(int kind, int N, int M, int K, const int *cam_idx, const int *p
     return status;
 }
 
+/* ---- stage-by-stage yardsticks (tests/stage_checks.py) --------------------------------------------------------------------------------
+ * Each stage of a GPU trial is measured against the same stage in quad precision on the GPU's OWN inputs of that stage, so that no
+ * upstream difference enters its bound.  Inputs are doubles (an fp32 GPU value is exact in double), outputs are rounded to double. */
+
+/* Linearisation at a given state: residuals f (2K), Jc (K x 18), Jp (K x 6), g = -J'r (3M + 9N, [points | cameras]) and the energy.
+ * Returns 0, or -1 when out of memory. */
+int ref_linearize(int N, int M, int K, const int *cam_idx, const int *pt_idx, const double *meas, double tau, const double *cam15,
+                  const double *pts, double *f_out, double *Jc_out, double *Jp_out, double *g_out, double *energy_out)
+{
+    const size_t np = 3 * (size_t)M + 9 * (size_t)N;
+    S *c = (S *)malloc(sizeof(S) * 15 * (size_t)N), *p = (S *)malloc(sizeof(S) * 3 * (size_t)M);
+    S *ms = (S *)calloc(2 * (size_t)K + 1, sizeof(S)), *f = (S *)malloc(sizeof(S) * 2 * (size_t)K);
+    S *Jc = (S *)malloc(sizeof(S) * 18 * (size_t)K), *Jp = (S *)malloc(sizeof(S) * 6 * (size_t)K), *g = (S *)malloc(sizeof(S) * np);
+    int rc = -1;
+    if (c && p && ms && f && Jc && Jp && g) {
+        for (size_t i = 0; i < 15 * (size_t)N; i++) c[i] = cam15[i];
+        for (size_t i = 0; i < 3 * (size_t)M; i++) p[i] = pts[i];
+        for (size_t i = 0; i < 2 * (size_t)K; i++) ms[i] = meas[i];
+        const S e = ora_residuals_f128(N, M, K, c, p, cam_idx, pt_idx, ms, (S)tau, f);
+        ora_jacobian_f128(N, M, K, c, p, cam_idx, pt_idx, ms, (S)tau, Jc, Jp);
+        grad_diag_f128(N, M, K, cam_idx, pt_idx, Jc, Jp, f, g, NULL);
+        for (size_t i = 0; i < 2 * (size_t)K; i++) f_out[i] = (double)f[i];
+        for (size_t i = 0; i < 18 * (size_t)K; i++) Jc_out[i] = (double)Jc[i];
+        for (size_t i = 0; i < 6 * (size_t)K; i++) Jp_out[i] = (double)Jp[i];
+        for (size_t i = 0; i < np; i++) g_out[i] = (double)g[i];
+        *energy_out = (double)e;
+        rc = 0;
+    }
+    free(c); free(p); free(ms); free(f); free(Jc); free(Jp); free(g);
+    return rc;
+}
+
+/* The elimination and reduced camera system of one trial from GIVEN J and residuals (no re-linearisation, unlike ref_reduced):
+ * S_out (D x D column-major, may be NULL), rhs_out (D), g_out (3M + 9N, may be NULL); dx_out (3M + 9N, may be NULL): when given,
+ * the whole step of the symbol is solved too (in quad, minutes beyond D ~ 400), otherwise only the system is assembled.
+ * kind as ora_step (observations sorted by point).  Returns ora_step's code, or -1 when out of memory. */
+int ref_reduced_from_jacobian(int kind, int N, int M, int K, const int *cam_idx, const int *pt_idx, const double *Jc_in,
+                              const double *Jp_in, const double *f_in, double lambda, double *S_out, double *rhs_out, double *g_out,
+                              double *dx_out)
+{
+    const size_t np = 3 * (size_t)M + 9 * (size_t)N, D = 9 * (size_t)N;
+    S *f = (S *)malloc(sizeof(S) * 2 * (size_t)K), *Jc = (S *)malloc(sizeof(S) * 18 * (size_t)K), *Jp = (S *)malloc(sizeof(S) * 6 * (size_t)K);
+    S *dx = (S *)calloc(np, sizeof(S)), *g = (S *)malloc(sizeof(S) * np), *rq = (S *)malloc(sizeof(S) * D);
+    S *Sq = S_out ? (S *)malloc(sizeof(S) * D * D) : NULL;
+    int rc = -1;
+    if (f && Jc && Jp && dx && g && rq && (Sq || !S_out)) {
+        for (size_t i = 0; i < 2 * (size_t)K; i++) f[i] = f_in[i];
+        for (size_t i = 0; i < 18 * (size_t)K; i++) Jc[i] = Jc_in[i];
+        for (size_t i = 0; i < 6 * (size_t)K; i++) Jp[i] = Jp_in[i];
+        rc = ora_step_f128(dx_out ? kind : (kind | 256), N, M, K, cam_idx, pt_idx, Jc, Jp, f, (S)lambda, dx, Sq, rq, g, NULL);
+        if (!rc) {
+            if (S_out)
+                for (size_t i = 0; i < D * D; i++) S_out[i] = (double)Sq[i];
+            for (size_t i = 0; i < D; i++) rhs_out[i] = (double)rq[i];
+            if (g_out)
+                for (size_t i = 0; i < np; i++) g_out[i] = (double)g[i];
+            if (dx_out)
+                for (size_t i = 0; i < np; i++) dx_out[i] = (double)dx[i];
+        }
+    }
+    free(f); free(Jc); free(Jp); free(dx); free(g); free(rq); free(Sq);
+    return rc;
+}
+
+/* The trial point x (+) dx in quad (BAFunctor::update_params through ora_retract). */
+int ref_retract(int N, int M, const double *cam15, const double *pts, const double *dx, double *cam_out, double *pts_out)
+{
+    const size_t np = 3 * (size_t)M + 9 * (size_t)N;
+    S *c = (S *)malloc(sizeof(S) * 15 * (size_t)N), *p = (S *)malloc(sizeof(S) * 3 * (size_t)M), *d = (S *)malloc(sizeof(S) * np);
+    S *co = (S *)malloc(sizeof(S) * 15 * (size_t)N), *po = (S *)malloc(sizeof(S) * 3 * (size_t)M);
+    int rc = -1;
+    if (c && p && d && co && po) {
+        for (size_t i = 0; i < 15 * (size_t)N; i++) c[i] = cam15[i];
+        for (size_t i = 0; i < 3 * (size_t)M; i++) p[i] = pts[i];
+        for (size_t i = 0; i < np; i++) d[i] = dx[i];
+        ora_retract_f128(N, M, c, p, d, co, po);
+        for (size_t i = 0; i < 15 * (size_t)N; i++) cam_out[i] = (double)co[i];
+        for (size_t i = 0; i < 3 * (size_t)M; i++) pts_out[i] = (double)po[i];
+        rc = 0;
+    }
+    free(c); free(p); free(d); free(co); free(po);
+    return rc;
+}
+
+/* Scaled residual of a symmetric solve S x = b, per row i:
+ *   num_i = |(S x - b)_i|,   den_i = sqrt(S_ii) * sum_j sqrt(S_jj) |x_j| + |b_i|
+ * so that max_i num_i / den_i is the componentwise backward error of an LDL^T solve of a positive definite S (|L| |D| |L'| is
+ * bounded entrywise by sqrt(S_ii S_jj)); it does not depend on cond(S).  S is column-major with leading dimension D, only its lower
+ * triangle is read, streamed column by column (no quad copy of S).  A product of two doubles is exact in quad, so the residual is
+ * the exact one up to the quad sum.  Returns 0, or -1 when out of memory. */
+int ref_sym_residual(int D, const double *Sm, const double *x, const double *b, double *num_out, double *den_out)
+{
+    S *r = (S *)malloc(sizeof(S) * (size_t)D), *sd = (S *)malloc(sizeof(S) * (size_t)D);
+    if (!r || !sd) { free(r); free(sd); return -1; }
+    S w = 0;
+    for (int i = 0; i < D; i++) {
+        r[i] = -(S)b[i];
+        sd[i] = sqrtq(fabsq((S)Sm[(size_t)i * D + i]));
+        w += sd[i] * fabsq((S)x[i]);
+    }
+    for (int j = 0; j < D; j++) {
+        const double *col = Sm + (size_t)j * D;
+        const S xj = x[j];
+        S acc = (S)col[j] * xj;
+        for (int i = j + 1; i < D; i++) {
+            const S s = col[i];
+            r[i] += s * xj;
+            acc += s * (S)x[i];
+        }
+        r[j] += acc;
+    }
+    for (int i = 0; i < D; i++) {
+        num_out[i] = (double)fabsq(r[i]);
+        den_out[i] = (double)(sd[i] * w + fabsq((S)b[i]));
+    }
+    free(r); free(sd);
+    return 0;
+}
+
 /* ---- the oracle a fourth time: S = long double (x87 extended: 64-bit significand, eps 1.1e-19 = fp64's / 2048) -----------------------
  * Round 4: a free run in this arithmetic costs ~3x an fp64 one (a __float128 run: ~1000x), so WHOLE ENSEMBLES of free runs are affordable.
  * They answer what single quad runs cannot: does the DISTRIBUTION of final energies of the reference algorithm depend on the size of the

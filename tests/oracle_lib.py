@@ -283,3 +283,69 @@ def referee_jacobian_fd(p, cam15, pts, tau=0.5):
     if rc:
         raise RuntimeError("ref_jacobian_fd failed: %d" % rc)
     return Jc, Jp
+
+
+# ---- stage-by-stage yardsticks in quad precision (oracle/ba_referee.c; tests/stage_checks.py) ------------------------------------------
+def referee_linearize(p, cam15, pts, tau=0.5):
+    """Residuals f (2K), Jc [K,2,9], Jp [K,2,3], g = -J'r (3M + 9N) and the energy, in quad at the double state (cam15, pts)."""
+    cam15 = np.ascontiguousarray(cam15, np.float64).reshape(-1)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1)
+    f = np.empty(2 * p.K)
+    Jc = np.empty((p.K, 2, 9))
+    Jp = np.empty((p.K, 2, 3))
+    g = np.empty(3 * p.M + 9 * p.N)
+    e = C.c_double()
+    rc = referee().ref_linearize(p.N, p.M, p.K, _p(p.cam_idx), _p(p.pt_idx), _p(p.meas), C.c_double(tau), _p(cam15), _p(pts), _p(f),
+                                 _p(Jc), _p(Jp), _p(g), C.byref(e))
+    if rc:
+        raise RuntimeError("ref_linearize rc=%d" % rc)
+    return dict(f=f, Jc=Jc, Jp=Jp, g=g, energy=e.value)
+
+
+def referee_reduced_from_jacobian(kind, p, Jc, Jp, f, lam, want_S=True, want_dx=False):
+    """Elimination + reduced camera system (S, rhs) and g in quad from GIVEN Jc, Jp, f (no re-linearisation); want_dx: the symbol's
+    whole step too (quad dense factorisation: small D only).  S comes back symmetric, D x D."""
+    D = p.D
+    np_ = 3 * p.M + D
+    Jc = np.ascontiguousarray(Jc, np.float64).reshape(-1)
+    Jp = np.ascontiguousarray(Jp, np.float64).reshape(-1)
+    f = np.ascontiguousarray(f, np.float64).reshape(-1)
+    S = np.empty(D * D) if want_S else None
+    rhs = np.empty(D)
+    g = np.empty(np_)
+    dx = np.empty(np_) if want_dx else None
+    rc = referee().ref_reduced_from_jacobian(kind, p.N, p.M, p.K, _p(p.cam_idx), _p(p.pt_idx), _p(Jc), _p(Jp), _p(f), C.c_double(lam),
+                                             _p(S), _p(rhs), _p(g), _p(dx))
+    if rc:
+        raise RuntimeError("ref_reduced_from_jacobian rc=%d" % rc)
+    return dict(S=None if S is None else S.reshape(D, D).T, rhs=rhs, g=g, dx=dx)
+
+
+def referee_retract(p, cam15, pts, dx):
+    """x (+) dx in quad from double inputs, rounded to double."""
+    cam15 = np.ascontiguousarray(cam15, np.float64).reshape(-1)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1)
+    dx = np.ascontiguousarray(dx, np.float64).reshape(-1)
+    co = np.empty(15 * p.N)
+    po = np.empty(3 * p.M)
+    rc = referee().ref_retract(p.N, p.M, _p(cam15), _p(pts), _p(dx), _p(co), _p(po))
+    if rc:
+        raise RuntimeError("ref_retract rc=%d" % rc)
+    return co, po
+
+
+def referee_sym_residual(S, x, b):
+    """(num, den) per row of the symmetric solve S x = b (oracle/ba_referee.c: ref_sym_residual): num = |S x - b| in quad,
+    den = sqrt(S_ii) sum_j sqrt(S_jj) |x_j| + |b_i|.  Only the lower triangle of S is read (no copy when S is Fortran-ordered)."""
+    S = np.asfortranarray(S, np.float64)
+    D = S.shape[0]
+    assert S.shape == (D, D)
+    x = np.ascontiguousarray(x, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    assert x.shape == b.shape == (D,)
+    num = np.empty(D)
+    den = np.empty(D)
+    rc = referee().ref_sym_residual(D, _p(S), _p(x), _p(b), _p(num), _p(den))
+    if rc:
+        raise RuntimeError("ref_sym_residual rc=%d" % rc)
+    return num, den

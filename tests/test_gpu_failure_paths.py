@@ -6,6 +6,8 @@ word, not as a silently rejected step.  Tested once, not a stress loop."""
 import numpy as np
 import pytest
 
+import stage_checks
+
 pytestmark = pytest.mark.gpu
 
 
@@ -44,6 +46,17 @@ def test_row_flag_timeout_is_recovered(ba, gpu_ok, capfd):
     # the solver stays in the launch-per-step mode: a second run needs no recovery and gives the same table from its new start
     r2 = s.minimize(max_trials=3)
     assert s.recoveries() == 1 and r2["trials"] == 3
+    # what that mode computes (k_ldlt_panel + k_ldlt_update per block column, k_ldlt_backpair for the three pairs of the six block
+    # columns): the backward error of its camera step in its own S and rhs (tests/stage_checks.py), at a small and a large lambda
+    # (measured on an MI355X: 5.5e-17).  k_ldlt_backstep (an odd count) is checked by test_gpu_stages.py::test_launch_per_pair_back_sweep.
+    s.keep_intermediates(True)
+    s.linearize()
+    for lam in (1e-10, 1.0):
+        s.try_step(lam)
+        eta = stage_checks.eta(s.get(ba.GET_S), s.get(ba.GET_DX)[3 * s.Ml:], s.get(ba.GET_RHS))
+        print("STAGE launch_per_step eta@%.0e %.3e 1e-15" % (lam, eta))
+        assert eta <= 1e-15, (lam, eta)
+    assert s.recoveries() == 1
     # a reduced system of one block column has no fused step to fail
     assert ba.Solver(ba.Problem.synthetic(6, 100, 400, 3), ba.QRCHOL, ba.F64).selftest(2) == 4
 

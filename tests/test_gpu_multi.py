@@ -63,9 +63,11 @@ def _worker(rank, world, port, kind, out_q):
             elif code == 2:  # BA_OP_BCAST | root << 8
                 dist.broadcast(c, src=root)
                 t.copy_(c)
-            elif code == 3:  # the rank's own chunk summed over the ranks; the other chunks stay what they were (unspecified by the ABI)
+            elif code == 3:  # the rank's own chunk summed over the ranks; the other chunks are unspecified by the ABI: NaN here
                 dist.all_reduce(c, op=dist.ReduceOp.SUM)
                 t[rank * count:(rank + 1) * count].copy_(c[rank * count:(rank + 1) * count])
+                t[:rank * count].fill_(float("nan"))
+                t[(rank + 1) * count:].fill_(float("nan"))
             else:
                 return 1
             stream.synchronize()
@@ -246,9 +248,11 @@ def _worker_dist_factor(rank, world, port, out_q, ncams=40):
             elif code == 2:  # BA_OP_BCAST | root << 8
                 dist.broadcast(c, src=root)
                 t.copy_(c)
-            elif code == 3:  # the rank's own chunk summed over the ranks; the other chunks stay what they were (unspecified by the ABI)
+            elif code == 3:  # the rank's own chunk summed over the ranks; the other chunks are unspecified by the ABI: NaN here
                 dist.all_reduce(c, op=dist.ReduceOp.SUM)
                 t[rank * count:(rank + 1) * count].copy_(c[rank * count:(rank + 1) * count])
+                t[:rank * count].fill_(float("nan"))
+                t[(rank + 1) * count:].fill_(float("nan"))
             else:
                 return 1
             stream.synchronize()

@@ -447,13 +447,9 @@ def test_schur_assembly_does_not_depend_on_the_dealing(ba, gpu_ok, prob21, monke
             assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and got[2] == ref[2], (wgs, bands, window)
 
 
-@pytest.mark.parametrize("kind", [1, 3, 13, 0])
-def test_long_tracks_qr_buckets(ba, O, gpu_ok, kind, monkeypatch):
-    """Per-point QR with tracks of 40 / 100 / 200 / 300 / 700 observations (one bucket of lanes-per-point each, the last
-    one with 16 observations per lane) next to ordinary short tracks; repeated observations of a camera by one point are
-    legal input -- also for the symbols that write J2bot densely (QRKIT, MOREQR: the blocks of such observations add up in the
-    camera's columns; rounds 2 - 3 refused them with BA_ERR_ARG)."""
-    kind, has_S = moreqr_route(kind, monkeypatch, O)
+def _long_track_problem(ba):
+    """Tracks of 40 / 100 / 200 / 300 / 700 observations (one per lanes-per-point bucket of the per-point QR) next to ordinary short
+    tracks, some observing a camera more than once; sorted by point."""
     p = ba.Problem.synthetic(12, 200, 800, 77)
     a = p.arrays()
     rng = np.random.default_rng(5)
@@ -468,9 +464,18 @@ def test_long_tracks_qr_buckets(ba, O, gpu_ok, kind, monkeypatch):
     order = np.argsort(np.array(pt_idx), kind="stable")
     cam_idx, pt_idx = np.array(cam_idx, np.int32)[order], np.array(pt_idx, np.int32)[order]
     meas = np.array(meas, np.float64)[order].ravel()
-    K = len(cam_idx)
-    pl = ba.Problem.from_arrays(p.N, p.M, K, cam_idx, pt_idx, meas, a["cams9"], a["pts"])
-    po = O.Problem(p.N, p.M, K, cam_idx, pt_idx, meas, a["cams9"], a["pts"])
+    return ba.Problem.from_arrays(p.N, p.M, len(cam_idx), cam_idx, pt_idx, meas, a["cams9"], a["pts"])
+
+
+@pytest.mark.parametrize("kind", [1, 3, 13, 0])
+def test_long_tracks_qr_buckets(ba, O, gpu_ok, kind, monkeypatch):
+    """Per-point QR with tracks of 40 / 100 / 200 / 300 / 700 observations (one bucket of lanes-per-point each, the last
+    one with 16 observations per lane) next to ordinary short tracks; repeated observations of a camera by one point are
+    legal input -- also for the symbols that write J2bot densely (QRKIT, MOREQR: the blocks of such observations add up in the
+    camera's columns; rounds 2 - 3 refused them with BA_ERR_ARG)."""
+    kind, has_S = moreqr_route(kind, monkeypatch, O)
+    pl = _long_track_problem(ba)
+    po = to_oracle(pl)
     cam = O.init_cams(po)
     f, e = O.residuals(po, cam, po.pts)
     Jc, Jp = O.jacobian(po, cam, po.pts)

@@ -678,7 +678,11 @@ __global__ __launch_bounds__(256) void k_qr_backsolve(const T *__restrict__ A, s
         if (tid < 64) { // wave 0: rows j0 .. j1 - 1, lane i holds b[j0 + i]
             const int i = tid;
             T bi = i < nb ? b[j0 + i] : (T)0;
-            const T dii = i < nb ? tri[64 * i + i] : (T)1;
+            T dii = i < nb ? tri[64 * i + i] : (T)1;
+            // R_ii = +-Inf (k_qr_chunk keeps beta = alpha for a pivot of +-Inf, and beta overflows where a column's norm does) would
+            // give y_i = 0 and a FINITE step, which the LM control -- it rejects a trial only through non-finite scalars -- could
+            // accept (tests/test_gpu_dense_qr.py, an Inf pivot): a NaN instead
+            if (!(dii - dii == (T)0)) dii = (T)__builtin_nanf("");
             for (int k = nb - 1; k >= 0; k--) {
                 const T yk = ba_readlane_dyn(bi, k) / ba_readlane_dyn(dii, k);
                 bi -= (i < k ? tri[64 * k + i] : (T)0) * yk;

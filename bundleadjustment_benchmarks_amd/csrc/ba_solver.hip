@@ -389,6 +389,14 @@ template <typename T> struct Solver final : SolverBase {
         if ((rc = d_pperm.upload(std::vector<int>(M1, 0 | (1 << 2) | (2 << 4))))) return rc; // identity (CHOLESKY never pivots)
         if (dense_qr()) {
             {
+                // k_qr_backsolve keeps the D right-hand sides and a 64 x 64 triangle in dynamic LDS: a D whose request exceeds the
+                // device's limit per workgroup (MI355X: 160 KiB, fp64 D <= 16 320) is refused -- its launch would fail
+                int dev = 0, lim = 0;
+                HIPCHK(hipGetDevice(&dev));
+                HIPCHK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+                if (sizeof(T) * ((size_t)D + 64 + 64 * 64) > (size_t)lim) return BA_ERR_ARG;
+            }
+            {
                 // diagnostic switch BA_QR_HW_SQRT (ba_qr.hip.h: ba_qr_sqrt), written at every creation: the flag is process-global
                 const char *ev = getenv("BA_QR_HW_SQRT");
                 const int on = ev ? atoi(ev) : 0; // 0 (default): v_sqrt_f32 + one Newton step, 1: the bare instruction, 2: sqrtf

@@ -341,6 +341,111 @@ int ref_sym_residual(int D, const double *Sm, const double *x, const double *b, 
     return 0;
 }
 
+/* ---- dense Householder QR (bundleadjustment_benchmarks_amd/csrc/ba_qr.hip.h) on its own inputs ------------------------------------------
+ * A: the matrix the QR was handed, m x (D + 1) column-major (leading dimension lda), the right-hand side b in column D; F: the factored
+ * matrix in the same layout (leading dimension ldf): R the upper triangle of its first D rows, Q^T b all of column D, c its head.
+ * Sums over the m rows in blocks of QR_BLK products in long double (64-bit significand; a product of two doubles rounds by 2^-64),
+ * the blocks added in quad: the sums are exact to a few 1e-19 of the sums of the absolute values, whatever m. */
+#define QR_BLK 256
+typedef long double LD;
+
+/* sum_k x[k incx] y[k incy] over k < n (y == NULL: sum x^2; absx: sum |x| |y|) */
+static S qr_dot(long n, const double *x, long incx, const double *y, long incy, int absx)
+{
+    S acc = 0;
+    for (long k0 = 0; k0 < n; k0 += QR_BLK) {
+        const long k1 = k0 + QR_BLK < n ? k0 + QR_BLK : n;
+        LD part = 0;
+        for (long k = k0; k < k1; k++) {
+            const LD a = x[k * incx], b = y ? y[k * incy] : x[k * incx];
+            part += absx ? fabsl(a) * fabsl(b) : a * b;
+        }
+        acc += (S)part;
+    }
+    return acc;
+}
+#define COL(M, ld, j) ((M) + (size_t)(j) * (ld))
+
+/* Backward error of the factor, entry by entry: num (D x D, column-major) |R'R - A'A|_ij, den ||a_i|| ||a_j|| (both triangles).
+ * m D^2 / 2 long-double products. */
+int ref_qr_gram(long m, int D, const double *A, long lda, const double *F, long ldf, double *num, double *den)
+{
+    S *nrm = (S *)malloc(sizeof(S) * (size_t)(D > 0 ? D : 1));
+    if (!nrm) return -1;
+    for (int i = 0; i < D; i++) nrm[i] = sqrtq(qr_dot(m, COL(A, lda, i), 1, NULL, 1, 0));
+    for (int j = 0; j < D; j++)
+        for (int i = 0; i <= j; i++) {
+            const S rr = qr_dot(i + 1, COL(F, ldf, i), 1, COL(F, ldf, j), 1, 0); /* (R'R)_ij = sum_{k <= i} R_ki R_kj */
+            const S d = fabsq(rr - qr_dot(m, COL(A, lda, i), 1, COL(A, lda, j), 1, 0));
+            num[(size_t)j * D + i] = num[(size_t)i * D + j] = (double)d;
+            den[(size_t)j * D + i] = den[(size_t)i * D + j] = (double)(nrm[i] * nrm[j]);
+        }
+    free(nrm);
+    return 0;
+}
+
+/* The same through probes z (nz x D, row-major): num_p = | ||R z||^2 - ||A z||^2 |, den_p = || |A| |z| ||^2 -- m D per probe. */
+int ref_qr_gram_probe(long m, int D, const double *A, long lda, const double *F, long ldf, int nz, const double *Z, double *num, double *den)
+{
+    LD *az = (LD *)malloc(sizeof(LD) * (size_t)(m > 0 ? m : 1)), *aa = (LD *)malloc(sizeof(LD) * (size_t)(m > 0 ? m : 1));
+    if (!az || !aa) { free(az); free(aa); return -1; }
+    for (int p = 0; p < nz; p++) {
+        const double *z = Z + (size_t)p * D;
+        for (long r = 0; r < m; r++) az[r] = aa[r] = 0;
+        for (int c = 0; c < D; c++) { /* (A z)_r: D terms per row in long double */
+            const double *col = COL(A, lda, c);
+            const LD zc = z[c], zabs = fabsl(zc);
+            for (long r = 0; r < m; r++) { az[r] += col[r] * zc; aa[r] += fabsl((LD)col[r]) * zabs; }
+        }
+        S n_az = 0, n_aa = 0, n_rz = 0;
+        for (long r0 = 0; r0 < m; r0 += QR_BLK) {
+            const long r1 = r0 + QR_BLK < m ? r0 + QR_BLK : m;
+            LD p1 = 0, p2 = 0;
+            for (long r = r0; r < r1; r++) { p1 += az[r] * az[r]; p2 += aa[r] * aa[r]; }
+            n_az += (S)p1;
+            n_aa += (S)p2;
+        }
+        for (int i = 0; i < D; i++) { /* (R z)_i = sum_{k >= i} R_ik z_k */
+            const S t = qr_dot(D - i, COL(F, ldf, i) + i, ldf, z + i, 1, 0);
+            n_rz += t * t;
+        }
+        num[p] = (double)fabsq(n_rz - n_az);
+        den[p] = (double)n_aa;
+    }
+    free(az); free(aa);
+    return 0;
+}
+
+/* The transformed right-hand side: hnum_i = |R'c - A'b|_i, hden_i = ||a_i|| ||b||; onum = | ||Q^T b||^2 - ||b||^2 |, oden = ||b||^2
+ * (Q^T b: all m entries of column D of F). */
+int ref_qr_rhs(long m, int D, const double *A, long lda, const double *F, long ldf, double *hnum, double *hden, double *onum, double *oden)
+{
+    const double *b = COL(A, lda, D), *qtb = COL(F, ldf, D);
+    const S bb = qr_dot(m, b, 1, NULL, 1, 0), nb = sqrtq(bb);
+    for (int i = 0; i < D; i++) {
+        const S rc = qr_dot(i + 1, COL(F, ldf, i), 1, qtb, 1, 0); /* (R'c)_i = sum_{k <= i} R_ki c_k */
+        hnum[i] = (double)fabsq(rc - qr_dot(m, COL(A, lda, i), 1, b, 1, 0));
+        hden[i] = (double)(sqrtq(qr_dot(m, COL(A, lda, i), 1, NULL, 1, 0)) * nb);
+    }
+    *onum = (double)fabsq(qr_dot(m, qtb, 1, NULL, 1, 0) - bb);
+    *oden = (double)bb;
+    return 0;
+}
+
+/* The back substitution R y = c alone (R: upper triangle of the first D rows of F; c: the head of column D): num_i = |R y - c|_i,
+ * den_i = (|R| |y| + |c|)_i -- its componentwise backward error. */
+int ref_tri_residual(int D, const double *F, long ldf, const double *y, double *num, double *den)
+{
+    const double *c = COL(F, ldf, D);
+    for (int i = 0; i < D; i++) {
+        const double *row = COL(F, ldf, i) + i; /* R_ik, k >= i */
+        num[i] = (double)fabsq(qr_dot(D - i, row, ldf, y + i, 1, 0) - (S)c[i]);
+        den[i] = (double)(qr_dot(D - i, row, ldf, y + i, 1, 1) + fabsq((S)c[i]));
+    }
+    return 0;
+}
+#undef COL
+
 /* ---- the oracle a fourth time: S = long double (x87 extended: 64-bit significand, eps 1.1e-19 = fp64's / 2048) -----------------------
  * Round 4: a free run in this arithmetic costs ~3x an fp64 one (a __float128 run: ~1000x), so WHOLE ENSEMBLES of free runs are affordable.
  * They answer what single quad runs cannot: does the DISTRIBUTION of final energies of the reference algorithm depend on the size of the

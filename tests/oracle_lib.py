@@ -349,3 +349,53 @@ def referee_sym_residual(S, x, b):
     if rc:
         raise RuntimeError("ref_sym_residual rc=%d" % rc)
     return num, den
+
+
+def _qr_cols(X, m, D):
+    """A matrix of the dense QR as its D + 1 columns, each contiguous: X[c, r] = entry (r, c), rows r >= m ignored."""
+    X = np.ascontiguousarray(X, np.float64)
+    assert X.ndim == 2 and X.shape[0] == D + 1 and X.shape[1] >= m, (X.shape, m, D)
+    return X, X.shape[1]
+
+
+def referee_qr_gram(Ab, F, m, D, Z=None):
+    """(num, den) of the factor's backward error (oracle/ba_referee.c): Ab the matrix the QR was handed and F the factored one,
+    both [D + 1 columns, >= m rows] (rhs in column D).  Z None: |R'R - A'A|_ij and ||a_i|| ||a_j|| (D x D); Z (nz x D): per
+    probe z, | ||R z||^2 - ||A z||^2 | and || |A| |z| ||^2."""
+    Ab, lda = _qr_cols(Ab, m, D)
+    F, ldf = _qr_cols(F, m, D)
+    if Z is None:
+        num, den = np.empty((D, D)), np.empty((D, D))
+        rc = referee().ref_qr_gram(C.c_long(m), D, _p(Ab), C.c_long(lda), _p(F), C.c_long(ldf), _p(num), _p(den))
+    else:
+        Z = np.ascontiguousarray(Z, np.float64)
+        assert Z.ndim == 2 and Z.shape[1] == D
+        num, den = np.empty(len(Z)), np.empty(len(Z))
+        rc = referee().ref_qr_gram_probe(C.c_long(m), D, _p(Ab), C.c_long(lda), _p(F), C.c_long(ldf), len(Z), _p(Z), _p(num), _p(den))
+    if rc:
+        raise RuntimeError("ref_qr_gram rc=%d" % rc)
+    return num, den
+
+
+def referee_qr_rhs(Ab, F, m, D):
+    """((num, den) of R'c - A'b per column, (num, den) of ||Q'b||^2 - ||b||^2) -- oracle/ba_referee.c: ref_qr_rhs."""
+    Ab, lda = _qr_cols(Ab, m, D)
+    F, ldf = _qr_cols(F, m, D)
+    hn, hd = np.empty(D), np.empty(D)
+    on, od = C.c_double(), C.c_double()
+    rc = referee().ref_qr_rhs(C.c_long(m), D, _p(Ab), C.c_long(lda), _p(F), C.c_long(ldf), _p(hn), _p(hd), C.byref(on), C.byref(od))
+    if rc:
+        raise RuntimeError("ref_qr_rhs rc=%d" % rc)
+    return (hn, hd), (on.value, od.value)
+
+
+def referee_tri_residual(F, D, y):
+    """(num, den) per row of the back substitution R y = c (R, c: the first D rows of F) -- oracle/ba_referee.c: ref_tri_residual."""
+    F, ldf = _qr_cols(F, D, D)
+    y = np.ascontiguousarray(y, np.float64)
+    assert y.shape == (D,)
+    num, den = np.empty(D), np.empty(D)
+    rc = referee().ref_tri_residual(D, _p(F), C.c_long(ldf), _p(y), _p(num), _p(den))
+    if rc:
+        raise RuntimeError("ref_tri_residual rc=%d" % rc)
+    return num, den

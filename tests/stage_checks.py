@@ -15,8 +15,12 @@ error: 0 for exact arithmetic, about the unit roundoff for a backward-stable sta
   retraction      x (+) dx entry by entry (quad) in units of eps x the entry's scale
   trial scalars   the test energy against quad at the same trial point; rho denominator and |dx| of the same dx and g (relative to
                   sums of absolute values for the rho denominator)
+  dense QR        (ba_qr.hip.h, on the matrix A | b it was handed and what it left: R, Q^T b in column D, y) gram: max |R'R - A'A|_ij /
+                  (|a_i| |a_j|), the factor's backward error (or, for large m D^2, | |Rz|^2 - |Az|^2 | / | |A||z| |^2 over column-scaled probes z);
+                  qtb_head: max |R'c - A'b|_i / (|a_i| |b|); orth: | |Q^T b|^2 - |b|^2 | / |b|^2 (a reflector that is not
+                  orthogonal); tri: max |R y - c|_i / (|R| |y| + |c|)_i, the back substitution alone
 The sums over observations of the gradient, back-substitution and trial-scalar metrics are in long double (64-bit significand: 2048x
-finer than fp64), the rest in quad.
+finer than fp64), the dense-QR sums in blocks of long double added in quad, the rest in quad.
 """
 import numpy as np
 
@@ -198,3 +202,23 @@ def trial_scalar_errors(p, lam, dx, g, e_test, rho_scale, dx_norm, cam_test, pts
     dn = np.sqrt((dxl * dxl).sum())
     return dict(e_test=abs(e_test - e_ref) / e_ref, rho_scale=float(abs(LD(rho_scale) - rs) / rs_abs),
                 dx_norm=float(abs(LD(dx_norm) - dn) / dn))
+
+
+def qr_metrics(Ab, F, m, D, y=None, probes=0, seed=0):
+    """The dense QR's metrics (module docstring) from Ab, the matrix the QR was handed, and F, the matrix it left -- both
+    [D + 1 columns, >= m rows], the right-hand side in column D -- and y (tri: None = not measured).  probes > 0: gram in the probe
+    form over that many Gaussian z (seeded), each entry divided by its column's norm: every column weighs the same in the probe
+    whatever the column scales."""
+    Z = None
+    if probes:
+        nrm = np.linalg.norm(np.asarray(Ab)[:D, :m], axis=1)
+        Z = np.random.default_rng(seed).standard_normal((probes, D)) / np.where(nrm > 0, nrm, 1.0)
+    num, den = O.referee_qr_gram(Ab, F, m, D, Z)
+    out = dict(gram=float(_ratio(num, den).max()))
+    (hn, hd), (on, od) = O.referee_qr_rhs(Ab, F, m, D)
+    out["qtb_head"] = float(_ratio(hn, hd).max())
+    out["orth"] = float(_ratio([on], [od]).max())
+    if y is not None:
+        tn, td = O.referee_tri_residual(F, D, y)
+        out["tri"] = float(_ratio(tn, td).max())
+    return out

@@ -260,3 +260,18 @@ def test_comm_file_with_another_launchs_nonce_is_never_taken(tmp_path):
     p = _reader(tmp_path, path, 0.0, env={"BA_COMM_NONCE": "this-launch", "BA_COMM_WAIT_S": "3"})
     rc, waited, head = p.communicate(timeout=60)[0].split()
     assert int(rc) != 0 and float(waited) >= 2.9
+
+
+@pytest.mark.gpu
+def test_dense_qr_refuses_a_D_beyond_the_backsolve_lds(ba):
+    """k_qr_backsolve asks for sizeof(T) (D + 64 + 4096) bytes of dynamic LDS (test_gpu_dense_qr.py::test_qr_backsolve_lds: it runs
+    up to the device's limit per workgroup, 160 KiB on MI355X).  A dense-QR symbol whose D exceeds it is refused at creation with
+    BA_ERR_ARG (4) instead of a launch that fails: fp64 at N = 1814 (D = 16 326); the same problem in fp32 is taken."""
+    p = ba.Problem.synthetic(1814, 600, 4000, 5)
+    D = p.D
+    for kind in (ba.QRKIT, ba.MOREQR, ba.QRSPQR):
+        with pytest.raises(ba.BAError) as e:
+            ba.Solver(p, kind, ba.F64)
+        assert e.value.code == 4, (kind, e.value)
+    assert 8 * (D + 64 + 4096) > 160 * 1024 >= 4 * (D + 64 + 4096), D
+    ba.Solver(p, ba.QRKIT, ba.F32)

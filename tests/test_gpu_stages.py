@@ -13,7 +13,8 @@ LDL^T and its back sweep only through the step (1e-6) or a normal-equations resi
                   test_gpu_configs.py::test_cfg5_full_size (D = 9216), test_gpu_failure_paths.py::test_row_flag_timeout_is_recovered
                   (safe factor: k_ldlt_panel + k_ldlt_update per block column, fp64)
   dense QR        (QRKIT, MOREQR: no S) eta of the GPU camera step against the quad S and rhs from the GPU's J: elimination error
-                  included, bound max(10 x an fp64 QR solver on the same J, floor)
+                  included, bound max(10 x an fp64 QR solver on the same J, floor); the QR alone, at every TSQR shape and on the
+                  matrices the solver factors: test_gpu_dense_qr.py
   back-subst.     per point, the rows of the normal equations with the GPU's J, g and step
   retraction      GET_CAMS_TEST / GET_POINTS_TEST against the quad retraction of the GPU's state and step, in ulps
   trial scalars   e_test against the quad energy at the GPU's trial point; rho denominator and |dx| against the same sums of the

@@ -43,3 +43,12 @@ def test_two_per_cu_variant_keeps_its_occupancy(tmp_path):
         assert vg + ag <= 256 and occ >= 2 and spill == 0, (k, usage[k])
     for k in one_per_cu:  # one workgroup per CU by its LDS request; it must not spill
         assert usage[k][3] == 0, (k, usage[k])
+
+
+def test_qr_harness_builds_with_the_library_flags(tmp_path):
+    """tests/qr_harness.hip (test_gpu_dense_qr.py's driver of the dense QR kernels) compiles with csrc/Makefile's own flags -- the
+    code the library runs, MFMA accumulators in VGPRs included."""
+    import qr_harness as QH
+    hipcc, flags = QH.makefile_flags()
+    assert {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-amdgpu-mfma-vgpr-form"} <= set(flags), flags
+    assert os.path.getsize(QH.build(tmp_path)) > 0

@@ -195,3 +195,111 @@ def test_linearization_and_retraction_metrics(O, sub21):
     rs = float(st["dx"] @ (lam * st["dx"] + st["g"]))
     sc = SC.trial_scalar_errors(p, lam, st["dx"], st["g"], et, rs, np.linalg.norm(st["dx"]), co, po)
     assert sc["e_test"] < 1e-13 and sc["rho_scale"] < 1e-14 and sc["dx_norm"] < 1e-14, sc
+
+
+# ---- dense QR (ba_qr.hip.h): R, Q^T b and the back substitution on their own inputs ------------------------------------------------
+def _qr_problem(m, D, seed, grade=0.0):
+    """[D + 1 columns, m + 3 rows] (three padding rows, as the kernels' matrices have): Gaussian columns, scaled by 10^U(-grade, grade)."""
+    rng = np.random.default_rng(seed)
+    Ab = np.zeros((D + 1, m + 3))
+    Ab[:, :m] = rng.standard_normal((D + 1, m)) * 10.0 ** rng.uniform(-grade, grade, (D + 1, 1))
+    return Ab
+
+
+def _factored(R_aug, shape, dtype=np.float64):
+    """F as the kernels leave it, from R of [A | b]: R on and above the diagonal of the first D rows, Q^T b = (c, rho, 0, ...)."""
+    F = np.zeros(shape, dtype)
+    n = R_aug.shape[0]
+    for c in range(n):
+        F[c, : c + 1] = R_aug[: c + 1, c]
+    return F
+
+
+def _backsolve(F, D):
+    R = F[:D, :D].T
+    c = F[D, :D]
+    y = np.zeros(D, F.dtype)
+    for i in range(D - 1, -1, -1):
+        y[i] = (c[i] - R[i, i + 1:] @ y[i + 1:]) / R[i, i]
+    return y
+
+
+def _householder(Ab, m, D, bad_tau=None, skip_rhs=None):
+    """Householder QR of [A | b] column by column (LAPACK's dlarfg convention) in fp64, with one planted defect: bad_tau = (j, s):
+    reflector j's tau times s (no longer orthogonal); skip_rhs = j: reflector j not applied to the right-hand side."""
+    X = Ab[:, :m].T.copy()
+    for j in range(D):
+        x = X[j:, j]
+        alpha, nx = x[0], np.linalg.norm(x[1:])
+        if nx == 0:
+            continue
+        beta = -np.copysign(np.hypot(alpha, nx), alpha)
+        v = x / (alpha - beta)
+        v[0] = 1.0
+        tau = (beta - alpha) / beta
+        if bad_tau is not None and bad_tau[0] == j:
+            tau *= bad_tau[1]
+        hi = D if skip_rhs == j else D + 1
+        X[j:, j + 1: hi] -= tau * np.outer(v, v @ X[j:, j + 1: hi])
+        X[j, j], X[j + 1:, j] = beta, 0.0
+    F = np.zeros_like(Ab)
+    F[:, :m] = X.T
+    for c in range(D):
+        F[c, c + 1:] = 0.0
+    return F
+
+
+@pytest.mark.parametrize("grade", [0.0, 8.0])
+def test_dense_qr_metrics(grade):
+    """The dense-QR metrics on an fp64 QR of [A | b] by numpy.linalg.qr (LAPACK): each at the unit roundoff, whatever the column scales
+    (grade 8: columns over 1e-8 ... 1e8, the spread of J2bot); an fp32 QR at the fp32 unit roundoff; the probe form of gram likewise.
+    Planted defects, each at least 100x the clean value of its metric: one R entry off by 1e-10 relative (gram, full and probe),
+    a reflector whose tau is off by 1e-8 relative (orth: no longer orthogonal), one reflector's update of the right-hand side
+    dropped (qtb_head), one back-substitution entry off by 1e-10 relative (tri).  A NaN fails every bound."""
+    m, D = 700, 45
+    Ab = _qr_problem(m, D, 7, grade)
+    R_aug = np.linalg.qr(Ab[:, :m].T, mode="r")
+    F = _factored(R_aug, Ab.shape)
+    y = _backsolve(F, D)
+    ok = SC.qr_metrics(Ab, F, m, D, y)
+    ok.update({"gram_probe": SC.qr_metrics(Ab, F, m, D, probes=4)["gram"]})
+    print(ok)
+    assert all(v < 2e-15 for v in ok.values()), ok
+    # fp32: numpy's QR in float32 of the same matrix rounded to float32
+    A32 = Ab.astype(np.float32)
+    F32 = _factored(np.linalg.qr(A32[:, :m].T, mode="r"), Ab.shape, np.float32)
+    ok32 = SC.qr_metrics(A32.astype(np.float64), F32.astype(np.float64), m, D, _backsolve(F32, D).astype(np.float64))
+    assert all(v < 2e-6 for v in ok32.values()), ok32
+    # the defects, against the clean value of a hand-made Householder QR (same convention as the kernels)
+    H = _householder(Ab, m, D)
+    base = SC.qr_metrics(Ab, H, m, D, _backsolve(H, D))
+    base["gram_probe"] = SC.qr_metrics(Ab, H, m, D, probes=4)["gram"]
+    assert all(v < 2e-15 for v in base.values()), base
+    floor = {k: max(v, ok[k], 1e-17) for k, v in base.items()}
+    Fb = H.copy()
+    Fb[D - 3, 5] *= 1 + 1e-10  # R_{5, D-3}
+    assert SC.qr_metrics(Ab, Fb, m, D)["gram"] >= 100 * floor["gram"]
+    assert SC.qr_metrics(Ab, Fb, m, D, probes=4)["gram"] >= 100 * floor["gram_probe"]
+    bad = SC.qr_metrics(Ab, _householder(Ab, m, D, bad_tau=(D // 2, 1 + 1e-8)), m, D)
+    assert bad["orth"] >= 100 * floor["orth"], (bad, floor)
+    bad = SC.qr_metrics(Ab, _householder(Ab, m, D, skip_rhs=D // 3), m, D)
+    assert bad["qtb_head"] >= 100 * floor["qtb_head"], (bad, floor)
+    yb = _backsolve(H, D)
+    yb[D // 2] *= 1 + 1e-10
+    assert SC.qr_metrics(Ab, H, m, D, yb)["tri"] >= 100 * floor["tri"]
+    # a NaN anywhere in what the kernels return fails every bound
+    for where in ("R", "c", "tail", "y"):
+        Fn, yn = H.copy(), _backsolve(H, D)
+        if where == "R":
+            Fn[D - 1, 3] = np.nan
+        elif where == "c":
+            Fn[D, 2] = np.nan
+        elif where == "tail":
+            Fn[D, m - 1] = np.nan
+        else:
+            yn[0] = np.nan
+        v = SC.qr_metrics(Ab, Fn, m, D, yn)
+        assert {"R": np.isnan(v["gram"]) and np.isnan(v["tri"]), "c": np.isnan(v["qtb_head"]) and np.isnan(v["orth"]),
+                "tail": np.isnan(v["orth"]), "y": np.isnan(v["tri"])}[where], (where, v)
+        if where == "R":
+            assert np.isnan(SC.qr_metrics(Ab, Fn, m, D, probes=2)["gram"])

@@ -13,6 +13,10 @@ cams.npy (N x 15, the solver's camera state), points.npy (M x 3; for N > 1 the r
 lm_result.npy ([final energy, lambda, status, iterations, trials] of the last ba_minimize() call).  The inputs are fixed by the
 arguments (a BAL file or a seeded synthetic problem), so two builds can be compared output for output.
 
+A plain run does only what the result line's headline needs: set-up, warm-up, the timed regions, the dump, the line.  --full adds, after
+all of that, what takes runs of its own (N = 1 only): the per-phase HIP-event replays (`phase_replay_ms`, --phase-reps), the roofline of
+the dominant kernel with the algorithmic bytes, and the CPU-oracle baseline (`cpu_baseline`, about 30 s; --no-cpu-baseline drops it).
+
 A "step" is one Levenberg-Marquardt trial = one row of the reference's iteration table
 (src/Eigen_ext/BacktrackLevMarqCholesky.h:308,322): point elimination, Schur assembly, dense LDL^T + solve,
 back-substitution, retraction, the test-energy evaluation and the step control, plus (once per accepted trial) the residual /
@@ -248,8 +252,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--regions", type=int, default=7, help="timed regions of --steps trials each (median reported)")
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--phase-reps", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also the phase replays, the roofline and the CPU-oracle baseline, after the timed regions (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU-oracle baseline")
+    ap.add_argument("--phase-reps", type=int, default=20, help="with --full: replays per phase")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed regions, write the outputs of the last one as DIR/<name>.npy (float64)")
     ap.add_argument("--dry-launch", action="store_true",
@@ -374,8 +380,8 @@ def main():
             # what the host adds per step on top of the device time of the trial and of the (conditional) linearisation behind it
             "host_overhead_ms_per_step": 1e3 * el / max(steps_done, 1) - (tm["trial_ms"] + tm["linearize_ms"]) / ntr,
         }
-    # roofline of the dominant kernel, measured live with HIP events on the solver's stream (rank 0, N=1 only)
-    if world == 1:
+    # --full: roofline of the dominant kernel, measured live with HIP events on the solver's stream (rank 0, N=1 only)
+    if args.full and world == 1:
         lam = 1e-4
         solver.set_state(cam0.reshape(prob.N, 15), pts0)
         solver.linearize(True)

@@ -7,7 +7,7 @@ C=$2
 shift 2
 mkdir -p $O
 for e in "" "$@"; do
-    env $e timeout -k 10 300 python3 $R/bench.py --workload $C --steps 30 --warmup 5 --no-cpu-baseline --phase-reps 10 > $O/b.json 2> $O/b.err || { tail -3 $O/b.err; exit 1; }
+    env $e timeout -k 10 300 python3 $R/bench.py --workload $C --steps 30 --warmup 5 --full --no-cpu-baseline --phase-reps 10 > $O/b.json 2> $O/b.err || { tail -3 $O/b.err; exit 1; }
     python3 -c "
 import json
 r=json.loads(open('$O/b.json').read().strip().splitlines()[-1])

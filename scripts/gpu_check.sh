@@ -11,7 +11,7 @@ if [ -n "$2" ]; then K=(-k "$2"); else K=(); fi
 timeout -k 10 1500 python3 -m pytest $R/tests -m gpu -q -rA --durations=12 -p no:cacheprovider "${K[@]}" > $O/pytest.log 2>&1
 echo "pytest rc=$?" | tee -a $O/pytest.log
 grep -E "passed|failed|error" $O/pytest.log | tail -3
-timeout -k 10 300 python3 $R/bench.py --steps 50 --warmup 5 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+timeout -k 10 300 python3 $R/bench.py --steps 50 --warmup 5 --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err
 echo "bench rc=$?"
 python3 - <<PY
 import json

@@ -6,7 +6,7 @@ TAG=${1:-prof}; WL=${2:-cfg4}; STEPS=${3:-40}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_$WL -o $WL --output-format csv -- python3 $R/bench.py --workload $WL --steps $STEPS --warmup 4 --no-cpu-baseline --phase-reps 4 > $O/prof_$WL.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_$WL -o $WL --output-format csv -- python3 $R/bench.py --workload $WL --steps $STEPS --warmup 4 --full --no-cpu-baseline --phase-reps 4 > $O/prof_$WL.log 2>&1
 echo "rocprof rc=$?"
 F=$(find $O/prof_$WL -name "*kernel_stats.csv" | head -1)
 cp $F $O/${WL}_kernel_stats.csv

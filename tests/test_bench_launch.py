@@ -79,3 +79,24 @@ def test_steps_are_exact_and_outputs_are_dumped(tmp_path):
         dumps.append(a)
     for n in dumps[0]:
         assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone_and_full_adds_the_rest():
+    """A plain run stops behind the timed regions: no phase replays, roofline or CPU baseline, which take runs of their own.  --full adds
+    the replays and the roofline (the CPU baseline too, unless --no-cpu-baseline) behind the same timed trials."""
+    lines = []
+    for extra in ((), ("--full", "--no-cpu-baseline", "--phase-reps", "2")):
+        out = run("--gpus", "1", "--workload", "cfg2", "--steps", "20", "--warmup", "2", "--regions", "1", *extra)
+        assert out.returncode == 0, out.stderr[-4000:]
+        got = [w for w in out.stdout.splitlines() if w.startswith("{")]
+        assert len(got) == 1, out.stdout
+        lines.append(json.loads(got[0]))
+    plain, full = lines
+    for d in lines:
+        assert d["metric"] == "LM iterations/sec" and d["unit"] == "LM iterations/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["steps"] == 20 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert not {"roofline", "phase_replay_ms", "algorithmic_bytes", "cpu_baseline"} & set(plain), sorted(plain)
+    assert {"roofline", "phase_replay_ms", "algorithmic_bytes"} <= set(full) and "cpu_baseline" not in full, sorted(full)
+    assert all(v > 0 for v in full["phase_replay_ms"].values()), full["phase_replay_ms"]
+    assert plain["final_energy"] == full["final_energy"]  # the same timed trials either way

@@ -1,6 +1,6 @@
 """Thin ctypes binding of libba_mi355x.so (include/ba_mi355x.h) for the parity tests and bench.py.
 
-The product is the C-ABI library + the Bundle_Adjustment_{QRKit,QRChol,Cholesky} executables (csrc/main.c); this
+The product is the C-ABI library + the Bundle_Adjustment_{QRKit,QRChol,Cholesky,...,IterSchur} executables (csrc/main.c); this
 module adds nothing to the data path.  It fails loudly when the HIP library is missing -- there is no CPU fallback.
 """
 import ctypes as C
@@ -13,8 +13,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libba_mi355x.so")
 
 QRKIT, QRCHOL, CHOLESKY, MOREQR, QRSPQR = 0, 1, 2, 3, 4
+ITERSCHUR = 5  # no reference counterpart: the reduced camera system by PCG, never formed (include/ba_mi355x.h)
 F64, F32 = 0, 1
-KIND_NAMES = {QRKIT: "QRKIT", QRCHOL: "QRCHOL", CHOLESKY: "CHOLESKY", MOREQR: "MOREQR", QRSPQR: "QRSPQR"}
+KIND_NAMES = {QRKIT: "QRKIT", QRCHOL: "QRCHOL", CHOLESKY: "CHOLESKY", MOREQR: "MOREQR", QRSPQR: "QRSPQR", ITERSCHUR: "ITERSCHUR"}
 STATUS = {-2: "NotStarted", -1: "Running", 0: "Success", 1: "ExceededLambdaMax", 2: "TooManyFunctionEvaluation",
           3: "MaxItersReached"}
 
@@ -29,6 +30,7 @@ EXPORTS = [
     "ba_solver_keep_intermediates", "ba_solver_set_state", "ba_solver_timing", "ba_solver_time_phase", "ba_device_info",
     "ba_version", "ba_shard_plan", "ba_problem_save_cache", "ba_problem_load_cache", "ba_solver_selftest",
     "ba_comm_unique_id", "ba_comm_id_via_file", "ba_comm_id_file_done", "ba_solver_comm_init", "ba_solver_recoveries",
+    "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes",
 ]
 
 
@@ -49,6 +51,11 @@ class Timing(C.Structure):
                 ("factor_ms", C.c_double), ("backsub_ms", C.c_double), ("test_eval_ms", C.c_double),
                 ("comm_ms", C.c_double), ("trial_ms", C.c_double), ("n_linearize", C.c_longlong), ("n_trials", C.c_longlong),
                 ("n_graph_trials", C.c_longlong)]
+
+
+class PCGStats(C.Structure):
+    _fields_ = [("solves", C.c_longlong), ("total_iters", C.c_longlong), ("last_iters", C.c_int), ("last_converged", C.c_int),
+                ("last_rel_residual", C.c_double)]
 
 
 TRIAL_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double)
@@ -109,6 +116,9 @@ def lib():
         L.ba_solver_comm_init.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_comm_id_file_done.argtypes = [C.c_char_p, C.c_int]
         L.ba_solver_recoveries.argtypes = [C.c_void_p]
+        L.ba_solver_set_pcg.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.ba_solver_pcg_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -294,6 +304,22 @@ class Solver:
     def recoveries(self):
         """Trials ba_minimize repeated through the launch-per-step factorisation after a hand-off time-out."""
         return int(lib().ba_solver_recoveries(self._h))
+
+    def set_pcg(self, max_iter, rel_tol):
+        """ITERSCHUR: at most max_iter PCG iterations per trial, stop at |r| <= rel_tol |rhs|."""
+        _chk(lib().ba_solver_set_pcg(self._h, int(max_iter), float(rel_tol)), "ba_solver_set_pcg")
+
+    def pcg_stats(self, reset=False):
+        """ITERSCHUR: solves and iterations counted on the device; the last solve's iterations, convergence and |rhs - S dx_c| / |rhs|."""
+        st = PCGStats()
+        _chk(lib().ba_solver_pcg_stats(self._h, C.byref(st), int(reset)), "ba_solver_pcg_stats")
+        return {k: getattr(st, k) for k, _ in PCGStats._fields_}
+
+    def device_bytes(self):
+        """Sum of the handle's device allocations."""
+        n = C.c_size_t()
+        _chk(lib().ba_solver_device_bytes(self._h, C.byref(n)), "ba_solver_device_bytes")
+        return n.value
 
     def selftest(self, which):
         """Returns the library's return code (not raised): the failure paths are what this hook exists to show."""

@@ -57,7 +57,9 @@ struct ba_structure {
 };
 
 // chunk_len: entries per chunk of a camera pair (one wavefront of k_schur_pairs); dchunk_len: observations per chunk of a camera (k_cam_gram)
-int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *out);
+// pairs = false (BA_ITERSCHUR, which never forms the reduced camera matrix): no camera pairs, entries or chunks (steps 3 and 4) --
+// npairs, E and nchunks stay 0 -- and none of their limits; the camera-sorted view (step 5) is built as always.
+int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *out, bool pairs = true);
 
 // RCCL transport (ba_comm.cpp); comm is an ncclComm_t
 int ba_rccl_init(void **comm_out, const void *id128, int rank, int world);

@@ -10,6 +10,7 @@
 #include "ba_kernels.hip.h"
 #include "ba_dense.hip.h"
 #include "ba_qr.hip.h"
+#include "ba_pcg.hip.h"
 
 #include <chrono>
 #include <cmath>
@@ -83,6 +84,9 @@ struct SolverBase {
     virtual int minimize(const ba_lm_params *lm, ba_trial_cb cb, void *user, ba_result *out) = 0;
     virtual int time_phase(int phase, int reps, double lambda, double *ms) = 0;
     virtual int selftest(int which) = 0;
+    virtual int set_pcg(int max_iter, double rel_tol) = 0;
+    virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
+    virtual size_t device_bytes() const = 0;
     bool poisoned = false; // the watchdog gave up on a launch that never finished: every later call fails, nothing is freed
     int recoveries = 0;    // trials repeated through the launch-per-step factorisation after a hand-off time-out
     ba_allreduce_fn ar_fn = nullptr;
@@ -156,6 +160,9 @@ template <typename T> struct Solver final : SolverBase {
     // points by QR and then factors S = (Jc'Jc + lambda I) - sum Z Z' by LDL^T: 20x faster, but normal equations.
     bool more_qr_on = true;
     bool dense_qr() const { return kind == BA_QRKIT || kind == BA_QRSPQR || more_qr(); }
+    // CHOLESKY's linearisation (AoS camera records, fused k_eval<T, true, 2>) and point elimination (k_elim_chol): CHOLESKY and BA_ITERSCHUR
+    bool chol_elim() const { return kind == BA_CHOLESKY || kind == BA_ITERSCHUR; }
+    bool iterative() const { return kind == BA_ITERSCHUR; } // the reduced system by PCG (ba_pcg.hip.h): no S, no camera pairs
     bool more_qr() const { return kind == BA_MOREQR && more_qr_on; }
     DevBuf<T> d_mQl, d_mQR, d_R22; // MOREQR: the inner point blocks' thin Q (lambda rows, R1 rows: [Ml][9] each); R22 | c2 of the outer QR, D x (D + 1)
     int outer_rows() const { return 2 * Kl + 3 * Ml + D; }               // J2bot (QRKIT / QRSPQR per trial; MOREQR per outer iteration, lambda = 0)
@@ -216,7 +223,8 @@ template <typename T> struct Solver final : SolverBase {
     {
         kind = k; rank = rk; world = wd;
         more_qr_on = !(getenv("BA_MOREQR_QR") != nullptr && atoi(getenv("BA_MOREQR_QR")) == 0);
-        int rc = ba_build_structure(p, rk, wd, BA_CHUNK, 32 /* lanes of a k_cam_gram group */, &sx);
+        if (iterative() && wd > 1) return BA_ERR_ARG; // (a sharded PCG would need an all-reduce of a D-vector per iteration)
+        int rc = ba_build_structure(p, rk, wd, BA_CHUNK, 32 /* lanes of a k_cam_gram group */, &sx, /*pairs*/ !iterative());
         if (rc) return rc;
         N = p->N; D = 9 * N; Ml = sx.Ml; Kl = sx.Kl;
         Dp = ((D + NAUG + NB - 1) / NB) * NB;
@@ -240,7 +248,7 @@ template <typename T> struct Solver final : SolverBase {
             if ((rc = d_eb.upload(eb))) return rc;
             fuse = getenv("BA_NO_FUSE") == nullptr;
         }
-        if (kind != BA_CHOLESKY && sx.kmax > 1024) return BA_ERR_ARG; // more than 1024 observations of one point: not supported by k_elim_qr
+        if (!chol_elim() && sx.kmax > 1024) return BA_ERR_ARG; // more than 1024 observations of one point: not supported by k_elim_qr
         if (!st) { HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); own_stream = true; }
         for (auto &e : ev) HIPCHK(hipEventCreate(&e));
         for (auto &sl : ring)
@@ -264,12 +272,12 @@ template <typename T> struct Solver final : SolverBase {
             if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0) wall_khz = khz;
         }
 #define UP(buf, vec) if ((rc = buf.upload(vec))) return rc
-        UP(d_obs_cam, sx.obs_cam); UP(d_obs_pt, sx.obs_pt); UP(d_pt_ptr, sx.pt_ptr); UP(d_pair_hi, sx.pair_hi);
+        UP(d_obs_cam, sx.obs_cam); UP(d_obs_pt, sx.obs_pt); UP(d_pt_ptr, sx.pt_ptr); UP(d_pair_hi, sx.pair_hi); // (BA_ITERSCHUR: no pairs)
         UP(d_pair_lo, sx.pair_lo);
         UP(d_pair_chunk_ptr, sx.pair_chunk_ptr); UP(d_dchunk_ptr, sx.dchunk_ptr); UP(d_cam_dchunk_ptr, sx.cam_dchunk_ptr);
         UP(d_cam_obs, sx.cam_obs); UP(d_qr_pts, sx.qr_pts);
 #undef UP
-        {
+        if (!iterative()) {
             // Records beyond the Infinity Cache (256 MB; config 5: 1 GB): the kernel is bound by the traffic between the L2s and
             // memory, and fewer wavefronts in flight walking the pair list side by side leave more of a row camera's records in the
             // L2 (2.23 -> 2.07 ms at config 5; nothing either way at config 4, whose 58 MB of records stay in the Infinity Cache).
@@ -382,7 +390,7 @@ template <typename T> struct Solver final : SolverBase {
             return rc;
         const size_t K1 = Kl > 0 ? Kl : 1, M1 = Ml > 0 ? Ml : 1;
 #define AL(buf, n) if ((rc = buf.alloc(n))) return rc
-        AL(d_r, 2 * K1); if (kind != BA_CHOLESKY) AL(d_Jc, 18 * K1); /* CHOLESKY: JcA alone */ AL(d_JcA, 20 * K1); AL(d_Jp, 6 * K1); AL(d_U0, 6 * M1); AL(d_gp, 3 * M1);
+        AL(d_r, 2 * K1); if (!chol_elim()) AL(d_Jc, 18 * K1); /* CHOLESKY, ITERSCHUR: JcA alone */ AL(d_JcA, 20 * K1); AL(d_Jp, 6 * K1); AL(d_U0, 6 * M1); AL(d_gp, 3 * M1);
         AL(d_V, (size_t)81 * N); AL(d_gc, (size_t)D);
         if (kind == BA_MOREQR) { AL(d_rec0, (size_t)BA_REC * K1); AL(d_dinv0, 3 * M1); AL(d_tvec0, 3 * M1); AL(d_tri0, 6 * M1); }
         if ((rc = d_lm.alloc(1))) return rc;
@@ -417,14 +425,28 @@ template <typename T> struct Solver final : SolverBase {
         }
         AL(d_gcg, (size_t)D); AL(d_dslab, (size_t)BA_SLAB * (sx.ndchunks > 0 ? sx.ndchunks : 1));
         AL(d_rec, (size_t)BA_REC * K1); AL(d_dinv, 3 * M1); AL(d_tvec, 3 * M1); AL(d_tri, 6 * M1);
-        AL(d_slab, (size_t)BA_SLAB * (sx.nchunks > 0 ? sx.nchunks : 1));
-        AL(d_S, (size_t)ld * (Dp + 64)); AL(d_Wp, (size_t)4 * ld * NB); AL(d_Winv, (size_t)((D + NB - 1) / NB) * NB * NB); AL(d_dxc, (size_t)2 * Dp + 2 * NB); /* the solution + the back sweep's hand-over vector */ AL(d_dxp, 3 * M1);
-        if ((rc = d_flags.alloc((size_t)Dp / NB + 2))) return rc;
+        if (iterative()) {
+            // no S, Wp, Winv, flags or pair slab: the solution, the PCG vectors, the block-Jacobi inverses and fp64 block partials
+            // (the camera pass's chunk partials live in d_dslab, which the linearisation has consumed by then)
+            pcg_gc = (N + 255) / 256; pcg_gq = (int)(((size_t)9 * N + 255) / 256);
+            if (pcg_gc < 1) pcg_gc = 1;
+            if (pcg_gq < 1) pcg_gq = 1;
+            AL(d_dxc, (size_t)D); AL(d_dxp, 3 * M1);
+            AL(d_pcg_M, (size_t)81 * N); AL(d_pcg_b, (size_t)D); AL(d_pcg_r, (size_t)D); AL(d_pcg_z, (size_t)D); AL(d_pcg_p, (size_t)D);
+            AL(d_pcg_y, (size_t)D); AL(d_pcg_w, 3 * M1);
+            if ((rc = d_pcg_part.alloc((size_t)6 * pcg_gc + 2 * (size_t)pcg_gq))) return rc; // r'z (3 slots), |r|^2 (3 slots), p'Sp, |rhs - S x|^2
+            if ((rc = d_pcg.alloc(1))) return rc;
+            HIPCHK(hipMemset(d_pcg.p, 0, sizeof(ba_pcg_dev)));
+        } else {
+            AL(d_slab, (size_t)BA_SLAB * (sx.nchunks > 0 ? sx.nchunks : 1));
+            AL(d_S, (size_t)ld * (Dp + 64)); AL(d_Wp, (size_t)4 * ld * NB); AL(d_Winv, (size_t)((D + NB - 1) / NB) * NB * NB); AL(d_dxc, (size_t)2 * Dp + 2 * NB); /* the solution + the back sweep's hand-over vector */ AL(d_dxp, 3 * M1);
+            if ((rc = d_flags.alloc((size_t)Dp / NB + 2))) return rc;
+        }
         AL(d_part_e, (size_t)gE); AL(d_part_pm, (size_t)gM);
         AL(d_part_bs, (size_t)2 * gB); AL(d_part_st, (size_t)4 * gK); AL(d_scal, NSCAL);
 #undef AL
-        HIPCHK(hipMemset(d_S.p, 0, sizeof(T) * d_S.n));
-        HIPCHK(hipMemset(d_Wp.p, 0, sizeof(T) * d_Wp.n));
+        if (d_S.p) HIPCHK(hipMemset(d_S.p, 0, sizeof(T) * d_S.n));
+        if (d_Wp.p) HIPCHK(hipMemset(d_Wp.p, 0, sizeof(T) * d_Wp.n));
         HIPCHK(hipMemset(d_scal.p, 0, sizeof(T) * NSCAL));
         HIPCHK(hipMemset(d_dxc.p, 0, sizeof(T) * d_dxc.n));
         HIPCHK(hipMemset(d_part_bs.p, 0, sizeof(T) * d_part_bs.n));
@@ -508,7 +530,7 @@ template <typename T> struct Solver final : SolverBase {
                                          commit ? d_pts[0].p : (T *)nullptr, fa)
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
         if (!jac) BA_EVAL(false, 0);
-        else if (kind == BA_CHOLESKY) { if (fused && fuse) BA_EVAL(true, 2, false); else BA_EVAL(true, 0, false); }
+        else if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false); else BA_EVAL(true, 0, false); }
         else if (fused && fuse) BA_EVAL(true, 1);
         else BA_EVAL(true, 0);
 #undef BA_EVAL
@@ -593,7 +615,7 @@ template <typename T> struct Solver final : SolverBase {
 
     void launch_eliminate()
     {
-        if (kind == BA_CHOLESKY) {
+        if (chol_elim()) {
             hipLaunchKernelGGL((k_elim_chol<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
                                d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
                                fuse ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
@@ -841,6 +863,98 @@ template <typename T> struct Solver final : SolverBase {
         hipLaunchKernelGGL((k_post_reduce<T>), dim3((Dp + 3) / 4), dim3(256), 0, st, D, Dp, ld, d_scal.p + SC_LAMBDA, d_S.p, d_gcg.p, d_dxc.p);
     }
 
+    // ---- BA_ITERSCHUR (ba_pcg.hip.h) ------------------------------------------------------------------------------------------------
+    DevBuf<T> d_pcg_M /* [N][81] B_a, then B_a^-1 */, d_pcg_b /* reduced rhs */, d_pcg_r, d_pcg_z, d_pcg_p, d_pcg_y /* S p */, d_pcg_w /* [3][Ml] point pass */;
+    DevBuf<double> d_pcg_part; // block partials: r'z [3][gc] | |r|^2 [3][gc] | p'Sp [gq] | |rhs - S x|^2 [gq]
+    DevBuf<ba_pcg_dev> d_pcg;
+    int pcg_gc = 1, pcg_gq = 1; // blocks of the per-camera and per-(camera, row) launches
+    int pcg_max_iter = BA_PCG_MAX_ITER_DEFAULT;
+    double pcg_rel_tol = BA_PCG_REL_TOL_DEFAULT;
+    double *pcg_part_rz() const { return d_pcg_part.p; }
+    double *pcg_part_rr() const { return d_pcg_part.p + (size_t)3 * pcg_gc; }
+    double *pcg_part_py() const { return d_pcg_part.p + (size_t)6 * pcg_gc; }
+    double *pcg_part_res() const { return d_pcg_part.p + (size_t)6 * pcg_gc + pcg_gq; }
+
+    // segment A behind k_elim_chol: block-Jacobi preconditioner, reduced rhs, g_c for the retraction's rho terms, x_0 = 0 and the
+    // recurrence's start (p_{-1} = 0, z_0, slot-0 partials, |rhs|^2)
+    void launch_pcg_prep()
+    {
+        if (sx.ndchunks > 0)
+            hipLaunchKernelGGL((k_pcg_prec_chunks<T>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p, d_obs_pt.p,
+                               d_rec.p, d_tvec.p, Ml, d_dslab.p);
+        hipLaunchKernelGGL((k_pcg_prec_reduce<T>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
+                           d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, d_pcg_M.p, d_pcg_b.p, d_gcg.p);
+        hipLaunchKernelGGL((k_pcg_prec_inv<T>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
+                           pcg_part_rz(), pcg_part_rr());
+        hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(256), 0, st, pcg_part_rr(), pcg_gc, d_pcg.p);
+    }
+    // y = S v: the point pass, then the camera pass (chunk partials in d_dslab, then per camera)
+    template <bool FINAL> void launch_pcg_matvec(int k, double tol2)
+    {
+        const T *lam = d_scal.p + SC_LAMBDA;
+        if (Ml > 0)
+            hipLaunchKernelGGL((k_pcg_point<T, 8, FINAL>), dim3((unsigned)(((size_t)Ml * 8 + 255) / 256)), dim3(256), 0, st, k, Ml, d_pt_ptr.p, d_obs_cam.p,
+                               d_rec.p, d_dinv.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, pcg_part_rz(), pcg_part_rr(), pcg_gc, tol2, d_pcg.p, d_pcg_w.p);
+        if (sx.ndchunks > 0)
+            hipLaunchKernelGGL((k_pcg_cam_chunks<T, FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p,
+                               d_obs_pt.p, d_rec.p, Ml, d_pcg_w.p, d_dslab.p, d_pcg.p);
+        hipLaunchKernelGGL((k_pcg_cam<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
+                           d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gc, d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p);
+    }
+    // segment B's solve: pcg_max_iter iterations of four launches (the ones behind convergence return at once), the product S x of the
+    // step and the statistics.  The solution is d_dxc, where launch_backsub_retract reads it.
+    void launch_pcg_solve()
+    {
+        const double tol2 = pcg_rel_tol * pcg_rel_tol;
+        for (int k = 0; k < pcg_max_iter; k++) {
+            launch_pcg_matvec<false>(k, tol2);
+            hipLaunchKernelGGL((k_pcg_update<T>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, d_pcg_r.p,
+                               pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gq, d_pcg.p);
+        }
+        launch_pcg_matvec<true>(pcg_max_iter, tol2);
+        // (a trial ba_minimize enqueued behind the row that ended the run is not counted: lm->stop is already set when it runs)
+        hipLaunchKernelGGL(k_pcg_finish, dim3(1), dim3(256), 0, st, pcg_max_iter, pcg_part_rr(), pcg_gc, pcg_part_res(), pcg_gq, tol2, d_pcg.p,
+                           step_level ? (const int *)nullptr : (const int *)&d_lm.p->stop);
+    }
+    int set_pcg(int max_iter, double rel_tol) override
+    {
+        if (!iterative() || max_iter < 1 || !(rel_tol > 0 && rel_tol < 1)) return BA_ERR_ARG;
+        pcg_max_iter = max_iter; pcg_rel_tol = rel_tol;
+        if (g_trial) { (void)hipGraphExecDestroy(g_trial); g_trial = nullptr; } // (captured with the old launch sequence)
+        return BA_OK;
+    }
+    int pcg_stats(ba_pcg_stats *out, int reset) override
+    {
+        if (!iterative()) return BA_ERR_ARG;
+        ba_pcg_dev h{};
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(&h, d_pcg.p, sizeof h, hipMemcpyDeviceToHost));
+        if (out) {
+            out->solves = h.solves; out->total_iters = h.total_iters; out->last_iters = h.last_iters;
+            out->last_converged = h.last_converged; out->last_rel_residual = h.last_rel_residual;
+        }
+        if (reset) {
+            h.solves = 0; h.total_iters = 0; h.last_iters = 0; h.last_converged = 0; h.last_rel_residual = 0;
+            HIPCHK(hipMemcpy(d_pcg.p, &h, sizeof h, hipMemcpyHostToDevice));
+        }
+        return BA_OK;
+    }
+    template <typename B> static size_t bytes_of(const B &b) { return b.p ? sizeof(*b.p) * b.n : 0; }
+    size_t device_bytes() const override
+    {
+        size_t n = 0;
+        for (const auto *b : {&d_obs_cam, &d_obs_pt, &d_pt_ptr, &d_pair_hi, &d_pair_lo, &d_pair_chunk_ptr, &d_dchunk_ptr, &d_cam_dchunk_ptr, &d_cam_obs,
+                              &d_qr_pts, &d_flags, &d_pperm, &d_wave_ptr, &d_red_pairs, &d_eb, &d_own_off})
+            n += bytes_of(*b);
+        for (const auto *b : {&d_r, &d_Jc, &d_Jp, &d_JcA, &d_U0, &d_gp, &d_V, &d_gc, &d_rec0, &d_dinv0, &d_tvec0, &d_tri0, &d_cam[0], &d_cam[1],
+                              &d_pts[0], &d_pts[1], &d_meas, &d_gcg, &d_dslab, &d_rec, &d_dinv, &d_tvec, &d_tri, &d_slab, &d_S, &d_pack, &d_Skeep,
+                              &d_Wp, &d_Winv, &d_dxc, &d_dxp, &d_part_e, &d_part_pm, &d_part_bs, &d_part_st, &d_scal, &d_qA, &d_qtau, &d_q1obs,
+                              &d_q1lam, &d_mQl, &d_mQR, &d_R22, &d_qB, &d_qAcopy, &d_dbgr, &d_dbg2, &d_stage, &d_pcg_M, &d_pcg_b, &d_pcg_r,
+                              &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
+            n += bytes_of(*b);
+        return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg);
+    }
+
     int set_lambda(T lambda)
     {
         *h_lam = lambda;
@@ -904,6 +1018,7 @@ template <typename T> struct Solver final : SolverBase {
         int rc;
         launch_eliminate();
         if ((rc = mark(EV_T1))) return rc;
+        if (iterative()) { launch_pcg_prep(); return mark(EV_T2); } // (single shard: nothing to exchange)
         launch_assemble();
         if ((rc = mark(EV_T2))) return rc;
         if (dense_qr()) return sharded() ? launch_qr_stack_pack() : BA_OK;
@@ -916,7 +1031,8 @@ template <typename T> struct Solver final : SolverBase {
         if (dist_on()) { if ((rc = launch_dist_unpack())) return rc; }
         else if (sharded() && !dense_qr() && (rc = launch_pack(true))) return rc;
         if ((rc = mark(EV_T3))) return rc;
-        if (dense_qr()) { if (sharded()) launch_qr_stack_solve(); else launch_qrkit_solve(); }
+        if (iterative()) launch_pcg_solve();
+        else if (dense_qr()) { if (sharded()) launch_qr_stack_solve(); else launch_qrkit_solve(); }
         else {
             launch_post_reduce();
             if (keep && step_level) {
@@ -1028,7 +1144,7 @@ template <typename T> struct Solver final : SolverBase {
         }
         case BA_GET_JC: {
             if (n != 18 * (size_t)Kl) return BA_ERR_ARG;
-            if (kind == BA_CHOLESKY) { // the AoS records [Kl][20] are the only copy
+            if (chol_elim()) { // the AoS records [Kl][20] are the only copy
                 if ((rc = dl(d_JcA.p, 20 * (size_t)Kl, h))) return rc;
                 for (int i = 0; i < Kl; i++)
                     for (int q = 0; q < 18; q++) out[18 * (size_t)i + q] = h[20 * (size_t)i + q];
@@ -1056,6 +1172,12 @@ template <typename T> struct Solver final : SolverBase {
         }
         case BA_GET_S:
         case BA_GET_RHS: {
+            if (iterative()) { // no S; the reduced rhs of the last trial stays in d_pcg_b
+                if (what == BA_GET_S || n != (size_t)D) return BA_ERR_ARG;
+                if ((rc = dl(d_pcg_b.p, (size_t)D, h))) return rc;
+                for (int c = 0; c < D; c++) out[c] = h[c];
+                return BA_OK;
+            }
             if (!d_Skeep.p) return BA_ERR_ARG;
             if ((rc = dl(d_Skeep.p, d_Skeep.n, h))) return rc;
             if (what == BA_GET_RHS) {
@@ -1418,6 +1540,7 @@ template <typename T> struct Solver final : SolverBase {
     // it wait for unknowns that are never published -- the production path's reaction to that must be BA_ERR_HIP.
     int selftest(int which) override
     {
+        if (iterative() && which != 3) return BA_ERR_ARG; // (no dense factorisation, no back sweep)
         if (which == 2) { // arm: the fused factorisation's row workgroups stay silent and the panel's wait is short -- the next
                           // ba_minimize meets BA_DEVERR_ROW_FLAG on its first trial and must recover through the launch-per-step path
             if ((D + NB - 1) / NB < 2 || safe_factor) return BA_ERR_ARG; // (a single block column has no fused step)
@@ -1443,6 +1566,7 @@ template <typename T> struct Solver final : SolverBase {
     int time_phase(int phase, int reps, double lambda_d, double *ms) override
     {
         if (reps < 1 || !ms) return BA_ERR_ARG;
+        if (iterative() && (phase == 3 || phase == 6 || phase == 7)) return BA_ERR_ARG; // (no S)
         double acc_ms = 0;
         int rcl = set_lambda((T)lambda_d);
         if (rcl) return rcl;
@@ -1455,6 +1579,7 @@ template <typename T> struct Solver final : SolverBase {
             case 2: launch_eliminate(); break;
             case 3: launch_assemble(); break; // (QRKIT: J2bot instead of S)
             case 4:
+                if (iterative()) { launch_pcg_prep(); launch_pcg_solve(); break; }
                 launch_assemble(); // the factorisation is in place: rebuild S first (timed separately by phase 3)
                 if (dense_qr()) launch_qrkit_solve();
                 else { launch_post_reduce(); launch_factor_solve(); }
@@ -1522,7 +1647,8 @@ int ba_solver_create(const ba_problem *p, ba_solver_kind kind, ba_scalar scalar,
                      ba_solver **out)
 {
     if (!p || !out || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) return BA_ERR_ARG;
-    if (kind != BA_QRKIT && kind != BA_QRCHOL && kind != BA_CHOLESKY && kind != BA_MOREQR && kind != BA_QRSPQR) return BA_ERR_ARG;
+    if (kind != BA_QRKIT && kind != BA_QRCHOL && kind != BA_CHOLESKY && kind != BA_MOREQR && kind != BA_QRSPQR && kind != BA_ITERSCHUR) return BA_ERR_ARG;
+    if (kind == BA_ITERSCHUR && shard_world > 1) return BA_ERR_ARG; // single shard (ba_mi355x.h)
     if (scalar != BA_F64 && scalar != BA_F32) return BA_ERR_ARG;
     *out = nullptr;
     int cnt = 0;
@@ -1626,5 +1752,14 @@ int ba_solver_time_phase(ba_solver *s, int phase, int reps, double lambda, doubl
 }
 
 int ba_solver_selftest(ba_solver *s, int which) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->selftest(which); }
+
+int ba_solver_set_pcg(ba_solver *s, int max_iter, double rel_tol) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_pcg(max_iter, rel_tol); }
+int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
+int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
+{
+    if (!s || !bytes) return BA_ERR_ARG;
+    *bytes = s->impl->device_bytes();
+    return BA_OK;
+}
 
 } // extern "C"

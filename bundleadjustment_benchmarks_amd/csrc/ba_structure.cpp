@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <numeric>
 
-int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *s)
+int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *s, bool pairs)
 {
     if (!p || !s || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world || chunk_len < 1 || dchunk_len < 1) return BA_ERR_ARG;
     const int N = p->N, M = p->M, K = p->K;
@@ -71,60 +71,62 @@ int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int
     }
 
     // 3. camera pairs (hi >= lo), pair id = hi (hi + 1) / 2 + lo.
-    const long long np = (long long)N * (N + 1) / 2;
-    if (np > 0x7fffffffLL) return BA_ERR_ARG;
-    s->npairs = (int)np;
-    s->pair_hi.resize(np);
-    s->pair_lo.resize(np);
-    for (int hi = 0, q = 0; hi < N; hi++)
-        for (int lo = 0; lo <= hi; lo++, q++) { s->pair_hi[q] = hi; s->pair_lo[q] = lo; }
-    auto pid = [](int a, int b) -> long long {
-        const int hi = std::max(a, b), lo = std::min(a, b);
-        return (long long)hi * (hi + 1) / 2 + lo;
-    };
-    // count entries per pair.  For one point with observations i < i': entry (row = the one with the larger camera).
-    // Two observations of the SAME camera in one point (not in BAL data, allowed) give both orders on the diagonal pair.
-    std::vector<long long> pcount((size_t)np + 1, 0);
-    for (int j = 0; j < Ml; j++) {
-        const int b = s->pt_ptr[j], e = s->pt_ptr[j + 1];
-        for (int i = b; i < e; i++)
-            for (int i2 = b; i2 <= i; i2++) {
-                const long long q = pid(s->obs_cam[i], s->obs_cam[i2]);
-                pcount[q + 1] += (i != i2 && s->obs_cam[i] == s->obs_cam[i2]) ? 2 : 1;
-            }
-    }
-    for (long long q = 0; q < np; q++) pcount[q + 1] += pcount[q];
-    s->E = pcount[np];
-    if (s->E > 0x7fffffffLL) return BA_ERR_NOMEM;
-    s->ent_r.resize((size_t)s->E);
-    s->ent_c.resize((size_t)s->E);
-    {
-        std::vector<long long> cur(pcount.begin(), pcount.end() - 1);
-        for (int j = 0; j < Ml; j++) { // increasing point order inside each pair: fixed summation order
+    if (pairs) {
+        const long long np = (long long)N * (N + 1) / 2;
+        if (np > 0x7fffffffLL) return BA_ERR_ARG;
+        s->npairs = (int)np;
+        s->pair_hi.resize(np);
+        s->pair_lo.resize(np);
+        for (int hi = 0, q = 0; hi < N; hi++)
+            for (int lo = 0; lo <= hi; lo++, q++) { s->pair_hi[q] = hi; s->pair_lo[q] = lo; }
+        auto pid = [](int a, int b) -> long long {
+            const int hi = std::max(a, b), lo = std::min(a, b);
+            return (long long)hi * (hi + 1) / 2 + lo;
+        };
+        // count entries per pair.  For one point with observations i < i': entry (row = the one with the larger camera).
+        // Two observations of the SAME camera in one point (not in BAL data, allowed) give both orders on the diagonal pair.
+        std::vector<long long> pcount((size_t)np + 1, 0);
+        for (int j = 0; j < Ml; j++) {
             const int b = s->pt_ptr[j], e = s->pt_ptr[j + 1];
             for (int i = b; i < e; i++)
                 for (int i2 = b; i2 <= i; i2++) {
-                    const int ca = s->obs_cam[i], cb = s->obs_cam[i2];
-                    const long long q = pid(ca, cb);
-                    if (ca >= cb) { s->ent_r[cur[q]] = i; s->ent_c[cur[q]] = i2; cur[q]++; }
-                    else { s->ent_r[cur[q]] = i2; s->ent_c[cur[q]] = i; cur[q]++; }
-                    if (i != i2 && ca == cb) { s->ent_r[cur[q]] = i2; s->ent_c[cur[q]] = i; cur[q]++; }
+                    const long long q = pid(s->obs_cam[i], s->obs_cam[i2]);
+                    pcount[q + 1] += (i != i2 && s->obs_cam[i] == s->obs_cam[i2]) ? 2 : 1;
                 }
         }
-    }
-    // 4. chunks
-    s->pair_chunk_ptr.assign((size_t)np + 1, 0);
-    s->chunk_ptr.clear();
-    s->chunk_pair.clear();
-    for (long long q = 0; q < np; q++) {
-        for (long long b = pcount[q]; b < pcount[q + 1]; b += chunk_len) {
-            s->chunk_ptr.push_back((int)b);
-            s->chunk_pair.push_back((int)q);
+        for (long long q = 0; q < np; q++) pcount[q + 1] += pcount[q];
+        s->E = pcount[np];
+        if (s->E > 0x7fffffffLL) return BA_ERR_NOMEM;
+        s->ent_r.resize((size_t)s->E);
+        s->ent_c.resize((size_t)s->E);
+        {
+            std::vector<long long> cur(pcount.begin(), pcount.end() - 1);
+            for (int j = 0; j < Ml; j++) { // increasing point order inside each pair: fixed summation order
+                const int b = s->pt_ptr[j], e = s->pt_ptr[j + 1];
+                for (int i = b; i < e; i++)
+                    for (int i2 = b; i2 <= i; i2++) {
+                        const int ca = s->obs_cam[i], cb = s->obs_cam[i2];
+                        const long long q = pid(ca, cb);
+                        if (ca >= cb) { s->ent_r[cur[q]] = i; s->ent_c[cur[q]] = i2; cur[q]++; }
+                        else { s->ent_r[cur[q]] = i2; s->ent_c[cur[q]] = i; cur[q]++; }
+                        if (i != i2 && ca == cb) { s->ent_r[cur[q]] = i2; s->ent_c[cur[q]] = i; cur[q]++; }
+                    }
+            }
         }
-        s->pair_chunk_ptr[q + 1] = (int)s->chunk_ptr.size();
-    }
-    s->nchunks = (int)s->chunk_pair.size();
-    s->chunk_ptr.push_back((int)s->E);
+        // 4. chunks
+        s->pair_chunk_ptr.assign((size_t)np + 1, 0);
+        s->chunk_ptr.clear();
+        s->chunk_pair.clear();
+        for (long long q = 0; q < np; q++) {
+            for (long long b = pcount[q]; b < pcount[q + 1]; b += chunk_len) {
+                s->chunk_ptr.push_back((int)b);
+                s->chunk_pair.push_back((int)q);
+            }
+            s->pair_chunk_ptr[q + 1] = (int)s->chunk_ptr.size();
+        }
+        s->nchunks = (int)s->chunk_pair.size();
+        s->chunk_ptr.push_back((int)s->E);
+    } // pairs
 
     // 5. camera-sorted view of the observations (= self entries of the diagonal pairs), in chunks of dchunk_len.
     std::vector<int> cptr((size_t)N + 1, 0);

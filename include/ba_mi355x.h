@@ -49,7 +49,14 @@ enum {
  * Sharded (shard_world > 1), BA_QRKIT and BA_QRSPQR keep their dense QR: every shard factors its own rows of J2bot, the exchange step
  * sums a zeroed stack into which each shard has put its D x D triangle R (+ the head of Q^T rhs, g_c, energy), and the QR of the stack
  * runs redundantly (distributed TSQR) -- never the normal equations these symbols exist to avoid. */
-typedef enum { BA_QRKIT = 0, BA_QRCHOL = 1, BA_CHOLESKY = 2, BA_MOREQR = 3, BA_QRSPQR = 4 } ba_solver_kind;
+/* BA_ITERSCHUR (no reference counterpart, no parity claim with any reference trajectory): CHOLESKY's linearisation and point elimination,
+ * then the reduced camera system S dx_c = rhs -- the same S and rhs CHOLESKY assembles, lambda on the diagonal -- solved by block-Jacobi
+ * preconditioned conjugate gradients from dx_c = 0, with products by S computed from the elimination's records and S never formed.  A
+ * step is inexact: the iteration stops at |rhs - S dx_c| <= rel_tol |rhs| (recurrence residual) or after max_iter iterations
+ * (ba_solver_set_pcg; defaults BA_PCG_MAX_ITER_DEFAULT, BA_PCG_REL_TOL_DEFAULT).  The LM loop is CHOLESKY's; its rhoScale
+ * dx'(lambda dx + g) is then an approximation of the model decrease.  Device memory O(K + 81 N) (ba_solver_device_bytes), no D x D
+ * matrix and none of the dense symbols' limits on N or K; single shard only (shard_world > 1: BA_ERR_ARG).  BA_GET_S: BA_ERR_ARG. */
+typedef enum { BA_QRKIT = 0, BA_QRCHOL = 1, BA_CHOLESKY = 2, BA_MOREQR = 3, BA_QRSPQR = 4, BA_ITERSCHUR = 5 } ba_solver_kind;
 
 /* `typedef double Scalar;` / `typedef float Scalar;` (src/BATypeUtils.h:6-7). */
 typedef enum { BA_F64 = 0, BA_F32 = 1 } ba_scalar;
@@ -168,7 +175,9 @@ int ba_comm_id_file_done(const char *path, int rank);
  * to HBM in SoA layout, builds the static camera-pair structure.  Points (and their observations) are partitioned
  * into shard_world contiguous ranges balanced by observation count; this handle owns range shard_rank.
  * device < 0 keeps the current HIP device. Fails with BA_ERR_HIP when no GPU is present, with BA_ERR_ARG when a QR symbol
- * meets a point with more than 1024 observations (the per-point QR keeps a track in registers; CHOLESKY has no limit). */
+ * meets a point with more than 1024 observations (the per-point QR keeps a track in registers; CHOLESKY and BA_ITERSCHUR have no
+ * limit), with BA_ERR_ARG for BA_ITERSCHUR with shard_world > 1 and for a dense symbol with N > 65 535 cameras (host side, before any
+ * device allocation). */
 int ba_solver_create(const ba_problem *p, ba_solver_kind kind, ba_scalar scalar, int device, int shard_rank,
                      int shard_world, ba_solver **out);
 void ba_solver_free(ba_solver *s);
@@ -200,8 +209,8 @@ typedef enum {
     BA_GET_JC = 1,        /* 18K per obs 2x9 row-major, columns [T, omega, f, k1, k2] */
     BA_GET_JP = 2,        /* 6K  per obs 2x3 row-major */
     BA_GET_GRAD = 3,      /* 3M+9N  = -J'r, points first */
-    BA_GET_S = 4,         /* D*D column-major reduced camera matrix (full symmetric) of the last try_step */
-    BA_GET_RHS = 5,       /* D reduced right-hand side */
+    BA_GET_S = 4,         /* D*D column-major reduced camera matrix (full symmetric) of the last try_step (BA_ITERSCHUR: none) */
+    BA_GET_RHS = 5,       /* D reduced right-hand side (BA_ITERSCHUR: always kept) */
     BA_GET_DX = 6,        /* 3M+9N step of the last try_step */
     BA_GET_CAMS = 7,      /* 15N  R(9 row-major), T(3), f, k1, k2 */
     BA_GET_POINTS = 8,    /* 3M */
@@ -219,8 +228,8 @@ int ba_solver_set_state(ba_solver *s, const double *cam15, const double *pts);
 typedef struct {
     double linearize_ms;  /* residual + Jacobian + gradient / J_c^T J_c, per outer iteration */
     double eliminate_ms;  /* per-point elimination (3x3 LDL^T or Householder QR) */
-    double schur_ms;      /* reduced camera matrix assembly */
-    double factor_ms;     /* dense LDL^T + triangular solves */
+    double schur_ms;      /* reduced camera matrix assembly (BA_ITERSCHUR: preconditioner + reduced rhs) */
+    double factor_ms;     /* dense LDL^T + triangular solves (BA_ITERSCHUR: the PCG solve) */
     double backsub_ms;    /* point back-substitution + retraction */
     double test_eval_ms;  /* residual at xTest + scalar reductions */
     double comm_ms;       /* device time of the all-reduces (HIP events around them on the solver's stream) */
@@ -232,7 +241,8 @@ int ba_solver_timing(ba_solver *s, ba_timing *out, int reset);
 /* Bench hooks: replay one phase `reps` times on the solver's stream and return the mean device ms per launch
  * (HIP events on that stream).  phase: 0 residual eval, 1 residual+Jacobian, 2 point elimination,
  * 3 Schur assembly, 4 Schur assembly + dense factor + solve, 5 back-substitution + retraction,
- * 6 dense factorisation only, 7 backward sweep only (6 / 7 rebuild S untimed before every repetition). */
+ * 6 dense factorisation only, 7 backward sweep only (6 / 7 rebuild S untimed before every repetition).
+ * BA_ITERSCHUR: 4 = preconditioner + rhs + the PCG solve; 3, 6 and 7 return BA_ERR_ARG (there is no S). */
 int ba_solver_time_phase(ba_solver *s, int phase, int reps, double lambda, double *ms_per_launch);
 
 /* A hand-off between workgroups of one launch that times out (the fused factorisation's row flag, the one-launch back sweep's
@@ -253,6 +263,29 @@ int ba_solver_recoveries(const ba_solver *s);
  * raise a device error word that is read back with the trial's scalars); BA_ERR_ARG when the reduced system has fewer than
  * four 64-wide block columns (a single group has nobody to wait for). */
 int ba_solver_selftest(ba_solver *s, int which);
+
+/* ---- BA_ITERSCHUR (no reference counterpart) ---------------------------------------------------------------------------------- */
+
+/* Defaults of a new BA_ITERSCHUR solver (profiles/r05_iterschur_*.txt: the measurements behind them). */
+#define BA_PCG_MAX_ITER_DEFAULT 100
+#define BA_PCG_REL_TOL_DEFAULT 1e-6
+/* max_iter >= 1 iterations at most per trial, stop at |r| <= rel_tol |rhs| (0 < rel_tol < 1).  Every iteration slot is enqueued (four
+ * launches; those behind convergence return at once), so max_iter bounds the launches of a trial too.  BA_ERR_ARG for another kind
+ * or a bad value. */
+int ba_solver_set_pcg(ba_solver *s, int max_iter, double rel_tol);
+/* Counted on the device by every solve (try_step, and every trial of ba_minimize up to the row that ends the run): solves, iterations
+ * summed over them; of the last solve its iterations, whether it met rel_tol, and |rhs - S dx_c| / |rhs| of its step (recomputed
+ * with one more product by S, not the recurrence's residual).  reset != 0 clears the counters after reading them.  BA_ERR_ARG for
+ * another kind. */
+typedef struct {
+    long long solves, total_iters;
+    int last_iters, last_converged;
+    double last_rel_residual;
+} ba_pcg_stats;
+int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset);
+/* Sum of the handle's device allocations in bytes (every kind; the buffers a sharded solve allocates on its first trial included once
+ * they exist). */
+int ba_solver_device_bytes(const ba_solver *s, size_t *bytes);
 
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);

@@ -19,6 +19,9 @@ KIND_NAMES = {QRKIT: "QRKIT", QRCHOL: "QRCHOL", CHOLESKY: "CHOLESKY", MOREQR: "M
 STATUS = {-2: "NotStarted", -1: "Running", 0: "Success", 1: "ExceededLambdaMax", 2: "TooManyFunctionEvaluation",
           3: "MaxItersReached"}
 
+# ba_solver_set_constant: bit q of a camera's mask word = camera parameter q (the camera block of GET_JC / GET_DX / GET_GRAD)
+FIX_T, FIX_OMEGA, FIX_POSE, FIX_INTRINSICS, FIX_CAMERA = 0x007, 0x038, 0x03F, 0x1C0, 0x1FF
+
 (GET_RESIDUALS, GET_JC, GET_JP, GET_GRAD, GET_S, GET_RHS, GET_DX, GET_CAMS, GET_POINTS, GET_CAMS_TEST,
  GET_POINTS_TEST) = range(11)
 
@@ -30,7 +33,7 @@ EXPORTS = [
     "ba_solver_keep_intermediates", "ba_solver_set_state", "ba_solver_timing", "ba_solver_time_phase", "ba_device_info",
     "ba_version", "ba_shard_plan", "ba_problem_save_cache", "ba_problem_load_cache", "ba_solver_selftest",
     "ba_comm_unique_id", "ba_comm_id_via_file", "ba_comm_id_file_done", "ba_solver_comm_init", "ba_solver_recoveries",
-    "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes",
+    "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes", "ba_solver_set_constant", "ba_problem_gauge_mask",
 ]
 
 
@@ -119,6 +122,8 @@ def lib():
         L.ba_solver_set_pcg.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.ba_solver_pcg_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_set_constant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_problem_gauge_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -212,6 +217,13 @@ class Problem:
     @property
     def D(self):
         return 9 * self.N
+
+    def gauge_mask(self, ref_cam=0):
+        """uint16[N] camera mask that fixes the similarity gauge: FIX_POSE on ref_cam + one component of T of the camera farthest
+        from it (ba_problem_gauge_mask)."""
+        m = np.zeros(self.N, np.uint16)
+        _chk(lib().ba_problem_gauge_mask(self._h, int(ref_cam), _p(m)), "ba_problem_gauge_mask")
+        return m
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -308,6 +320,22 @@ class Solver:
     def set_pcg(self, max_iter, rel_tol):
         """ITERSCHUR: at most max_iter PCG iterations per trial, stop at |r| <= rel_tol |rhs|."""
         _chk(lib().ba_solver_set_pcg(self._h, int(max_iter), float(rel_tol)), "ba_solver_set_pcg")
+
+    def set_constant(self, cam_mask=None, pt_fixed=None):
+        """Hold parameters constant from the next linearize() / minimize() on: cam_mask uint16[N] (FIX_* bits), pt_fixed bool / uint8[M]
+        of the problem (None: nothing of that kind; both None or all zero: the unmasked solver)."""
+        N, M = self.problem.N, self.problem.M
+        if cam_mask is not None:
+            cam_mask = np.asarray(cam_mask)
+            if cam_mask.shape != (N,) or cam_mask.dtype != np.uint16:
+                raise ValueError("cam_mask must be a uint16 array of shape (%d,), got %s %s" % (N, cam_mask.dtype, cam_mask.shape))
+            cam_mask = np.ascontiguousarray(cam_mask)
+        if pt_fixed is not None:
+            pt_fixed = np.asarray(pt_fixed)
+            if pt_fixed.shape != (M,) or pt_fixed.dtype not in (np.bool_, np.uint8):
+                raise ValueError("pt_fixed must be a bool or uint8 array of shape (%d,), got %s %s" % (M, pt_fixed.dtype, pt_fixed.shape))
+            pt_fixed = np.ascontiguousarray(pt_fixed.astype(np.uint8))
+        _chk(lib().ba_solver_set_constant(self._h, _p(cam_mask), _p(pt_fixed)), "ba_solver_set_constant")
 
     def pcg_stats(self, reset=False):
         """ITERSCHUR: solves and iterations counted on the device; the last solve's iterations, convergence and |rhs - S dx_c| / |rhs|."""

@@ -154,10 +154,15 @@ template <typename T> struct ba_fuse_args {
     const T *lam;
     T *U0, *gp, *rec, *dinv, *tvec, *tri;
     int *fresh;
+    const unsigned short *cmask; // MASK: per camera, bit q = camera column q held constant (ba_solver_set_constant)
+    const unsigned char *pfix;   // MASK: per point of the shard, != 0 = its three columns held constant
 };
 // SOA = false (CHOLESKY): the camera blocks are kept in the AoS records JcA alone -- k_cam_gram gathers them by camera, k_elim_chol reads
 // its own record -- and the 18 SoA streams Jc (144 of the 624 bytes this kernel writes per observation when fused) are not written.
-template <typename T, bool JAC, int FUSE = 0, bool SOA = true>
+// MASK (ba_solver_set_constant): the columns of the parameters held constant are written as zeros -- Jc, JcA, Jp and the fused Aj / Bj
+// alike, so that everything built from J (g, U, V, S, the records, J2bot, max diag J'J) is the masked J's.  A separate instantiation:
+// the unmasked launch stays the kernel it was.
+template <typename T, bool JAC, int FUSE = 0, bool SOA = true, bool MASK = false>
 __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__restrict__ cam, const T *__restrict__ pts,
                                               const int *__restrict__ obs_cam, const int *__restrict__ obs_pt,
                                               const T *__restrict__ meas, T tau2, T *__restrict__ r, T *__restrict__ Jc,
@@ -167,6 +172,7 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
                                               ba_fuse_args<T> fa = ba_fuse_args<T>{})
 {
     static_assert(FUSE == 0 || JAC, "the fused point part belongs to the linearisation");
+    static_assert(!MASK || JAC, "the mask is a property of the Jacobian");
     __shared__ T red[4];
     if (go && *go == 0) return; // device-side LM control: the trial in front of this linearisation was rejected (uniform)
     const int b0 = fa.eb ? fa.eb[blockIdx.x] : (int)blockIdx.x * 256;
@@ -186,6 +192,8 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
     if (valid) {
         const int ci = obs_cam[i];
         pj = obs_pt[i];
+        // MASK: bits 0..8 = the camera's columns, 9..11 = the point's
+        const unsigned fix = MASK ? (unsigned)fa.cmask[ci] | (fa.pfix[pj] ? 0xE00u : 0u) : 0u;
         T c[15];
 #pragma unroll
         for (int k = 0; k < 15; k++) c[k] = cam[(size_t)k * N + ci];
@@ -250,8 +258,9 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
             Jb[19] = f * (xu1 * r2u); Jb[20] = f * (xu1 * r4u);
 #pragma unroll
             for (int q = 0; q < 12; q++) {
-                const T t0 = o00 * Jb[q] + o01 * Jb[12 + q];
-                const T t1 = o01 * Jb[q] + o11 * Jb[12 + q];
+                T t0 = o00 * Jb[q] + o01 * Jb[12 + q];
+                T t1 = o01 * Jb[q] + o11 * Jb[12 + q];
+                if (MASK && ((fix >> q) & 1u)) { t0 = 0; t1 = 0; }
                 if (q < 9) {
                     if (SOA) {
                         Jc[(size_t)q * K + i] = t0;
@@ -1282,25 +1291,32 @@ __global__ __launch_bounds__(256) void k_panel_stage(int h, int p0, int ld, T *_
 // dx_p = tri^-1 (dinv o (t - sum_i Z_i^T dx_c[cam_i]))  (src/Eigen_ext/BacktrackLevMarqQRChol.h:343-360);
 // x_test = x + dx_p (src/Optimization/BAFunctor.h:335-338); partial sums of dx^T (lambda dx + JtRes) (:375) and |dx|^2.
 struct ba_cam_retract_args { int N; const void *cam, *dxc, *gc; void *cam_test, *scal; int dst; };
-template <typename T>
+// MASK (ba_solver_set_constant): the parameters held constant.  Whatever the reduced solve left on a fixed row of dx_c (exact 0 for LDL^T
+// and PCG, roundoff for the dense QR kinds, whose reflectors mix the row's sqrt(lambda) in) is read as 0 by the point steps and written
+// back as 0 by the camera block; a fixed point's step is 0; fixed parameters of xTest are copies of x (the same bits, -0 included).
+struct ba_fix_args { const unsigned short *cmask; const unsigned char *pfix; };
+template <typename T, bool MASK = false>
 __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam, const T *__restrict__ dxc, const T *__restrict__ gc,
-                                                const T *__restrict__ lam, T *__restrict__ cam_test, T *__restrict__ scal, int dst, T *red);
+                                                const T *__restrict__ lam, T *__restrict__ cam_test, T *__restrict__ scal, int dst, T *red,
+                                                const unsigned short *__restrict__ cmask = nullptr);
 
 // cr.N > 0: one more block at the end of the grid retracts the cameras (K8, below: a launch of its own otherwise); npart = the
 // number of point blocks = the row length of partial[2][npart].
-template <typename T, int LPP>
+template <typename T, int LPP, bool MASK = false>
 __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,
                                                  const T *__restrict__ rec, const T *__restrict__ dinv, const T *__restrict__ tvec,
                                                  const T *__restrict__ tri, const T *__restrict__ dxc, const T *__restrict__ gp,
                                                  const T *__restrict__ pts, const T *__restrict__ lam, T *__restrict__ dxp, T *__restrict__ pts_test,
                                                  T *__restrict__ partial /* [2][npart] */, const int *__restrict__ pperm /* column permutation of the point's 3x3 block */,
-                                                 int npart, ba_cam_retract_args cr)
+                                                 int npart, ba_cam_retract_args cr, ba_fix_args fx = ba_fix_args{})
 {
     // LPP lanes per point: each lane forms Z_i^T dx_c for its observations (i = g, g + LPP, ...), a butterfly sum over
     // the group gives the point's 3-vector, lane 0 of the group finishes the 3x3 triangular solve.
     __shared__ T red[4];
     if (cr.N > 0 && (int)blockIdx.x == npart) {
-        ba_retract_cams<T>(cr.N, (const T *)cr.cam, (const T *)cr.dxc, (const T *)cr.gc, lam, (T *)cr.cam_test, (T *)cr.scal, cr.dst, red);
+        // (MASK: it zeroes the fixed rows of dx_c while the point blocks read it -- they mask what they read, so either value is fine)
+        ba_retract_cams<T, MASK>(cr.N, (const T *)cr.cam, (const T *)cr.dxc, (const T *)cr.gc, lam, (T *)cr.cam_test, (T *)cr.scal, cr.dst, red,
+                                 fx.cmask);
         return;
     }
     const int gid = (blockIdx.x * 256 + threadIdx.x) / LPP, lg = threadIdx.x % LPP;
@@ -1309,10 +1325,12 @@ __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__
     T s0 = 0, s1 = 0, s2 = 0;
     for (int i = b + lg; i < e; i += LPP) {
         const T *Z = rec + (size_t)i * BA_REC;
-        const T *dc = dxc + 9 * obs_cam[i];
+        const int ci = obs_cam[i];
+        const T *dc = dxc + 9 * ci;
+        const unsigned cm = MASK ? (unsigned)fx.cmask[ci] : 0u;
 #pragma unroll
         for (int c = 0; c < 9; c++) {
-            const T d = dc[c];
+            const T d = (MASK && ((cm >> c) & 1u)) ? (T)0 : dc[c];
             s0 += Z[3 * c] * d; s1 += Z[3 * c + 1] * d; s2 += Z[3 * c + 2] * d;
         }
     }
@@ -1332,11 +1350,13 @@ __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__
         const T y0 = (u0 - tri[(size_t)Ml + j] * y1 - tri[2 * (size_t)Ml + j] * y2) / tri[j];
         // m_dx = colsPermutation() * m_dx (BacktrackLevMarqQRChol.h:360): position c of the pivoted block is coordinate perm[c]
         const int pp = pperm[j], q0 = pp & 3, q1 = (pp >> 2) & 3;
-        const T x0 = q0 == 0 ? y0 : q1 == 0 ? y1 : y2, x1 = q0 == 1 ? y0 : q1 == 1 ? y1 : y2, x2 = q0 == 2 ? y0 : q1 == 2 ? y1 : y2;
+        T x0 = q0 == 0 ? y0 : q1 == 0 ? y1 : y2, x1 = q0 == 1 ? y0 : q1 == 1 ? y1 : y2, x2 = q0 == 2 ? y0 : q1 == 2 ? y1 : y2;
+        const bool pfixed = MASK && fx.pfix[j] != 0;
+        if (pfixed) { x0 = 0; x1 = 0; x2 = 0; }
         dxp[j] = x0; dxp[(size_t)Ml + j] = x1; dxp[2 * (size_t)Ml + j] = x2;
-        pts_test[j] = pts[j] + x0;
-        pts_test[(size_t)Ml + j] = pts[(size_t)Ml + j] + x1;
-        pts_test[2 * (size_t)Ml + j] = pts[2 * (size_t)Ml + j] + x2;
+        pts_test[j] = pfixed ? pts[j] : pts[j] + x0;
+        pts_test[(size_t)Ml + j] = pfixed ? pts[(size_t)Ml + j] : pts[(size_t)Ml + j] + x1;
+        pts_test[2 * (size_t)Ml + j] = pfixed ? pts[2 * (size_t)Ml + j] : pts[2 * (size_t)Ml + j] + x2;
         rho = x0 * (lambda * x0 + gp[j]) + x1 * (lambda * x1 + gp[(size_t)Ml + j]) + x2 * (lambda * x2 + gp[2 * (size_t)Ml + j]);
         dn = x0 * x0 + x1 * x1 + x2 * x2;
     }
@@ -1348,18 +1368,23 @@ __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__
 // ---- K8 (cameras): BAFunctor::update_params (src/Optimization/BAFunctor.h:311-332) -----------------------------
 // T += dT; R <- Rodrigues(d omega) R (identity when |d omega| <= 1e-6, src/MathUtils.h:66-82); f, k1, k2 += .
 // Single block (N <= a few thousand cameras); also the camera part of the rho / |dx|^2 sums -> scal[dst..dst+1].
-template <typename T>
+template <typename T, bool MASK>
 __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam, const T *__restrict__ dxc,
                                                 const T *__restrict__ gc, const T *__restrict__ lam, T *__restrict__ cam_test,
-                                                T *__restrict__ scal, int dst, T *red)
+                                                T *__restrict__ scal, int dst, T *red, const unsigned short *__restrict__ cmask)
 {
     const T lambda = *lam;
     T rho = 0, dn = 0;
     for (int a = threadIdx.x; a < N; a += 256) {
         T p[9];
+        const unsigned cm = MASK ? (unsigned)cmask[a] : 0u;
 #pragma unroll
         for (int c = 0; c < 9; c++) {
             p[c] = dxc[9 * a + c];
+            if (MASK && ((cm >> c) & 1u)) {
+                p[c] = 0;
+                ((T *)dxc)[9 * a + c] = 0; // (BA_GET_DX shows the step that was taken)
+            }
             rho += p[c] * (lambda * p[c] + gc[9 * a + c]);
             dn += p[c] * p[c];
         }
@@ -1381,6 +1406,10 @@ __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam
                     dR[3 * rr + cc] = dR[3 * rr + cc] + c1 * J[3 * rr + cc] + c2 * j2;
                 }
         }
+        if (MASK && (cm & 0x38u)) {  // (BA_FIX_OMEGA) // (omega is held constant as a whole: dR = I, and R is copied rather than multiplied by it)
+#pragma unroll
+            for (int c = 0; c < 9; c++) cam_test[(size_t)c * N + a] = R0[c];
+        } else {
 #pragma unroll
         for (int rr = 0; rr < 3; rr++)
 #pragma unroll
@@ -1390,24 +1419,34 @@ __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam
                 for (int k = 0; k < 3; k++) s += dR[3 * rr + k] * R0[3 * k + cc];
                 cam_test[(size_t)(3 * rr + cc) * N + a] = s;
             }
+        }
+        if constexpr (MASK) { // T (slots 9..11) and f, k1, k2 (slots 12..14): a fixed one is copied
+#pragma unroll
+            for (int c = 0; c < 9; c++) {
+                if (c >= 3 && c < 6) continue;
+                const size_t o = (size_t)(c < 3 ? 9 + c : 6 + c) * N + a;
+                cam_test[o] = ((cm >> c) & 1u) ? cam[o] : cam[o] + p[c];
+            }
+        } else {
 #pragma unroll
         for (int c = 0; c < 3; c++) cam_test[(size_t)(9 + c) * N + a] = cam[(size_t)(9 + c) * N + a] + p[c];
         cam_test[(size_t)12 * N + a] = cam[(size_t)12 * N + a] + p[6];
         cam_test[(size_t)13 * N + a] = cam[(size_t)13 * N + a] + p[7];
         cam_test[(size_t)14 * N + a] = cam[(size_t)14 * N + a] + p[8];
+        }
     }
     rho = block_reduce<T, false>(rho, red);
     dn = block_reduce<T, false>(dn, red);
     if (threadIdx.x == 0) { scal[dst] = rho; scal[dst + 1] = dn; }
 }
 
-template <typename T>
+template <typename T, bool MASK = false>
 __global__ __launch_bounds__(256) void k_retract_cams(int N, const T *__restrict__ cam, const T *__restrict__ dxc,
                                                       const T *__restrict__ gc, const T *__restrict__ lam, T *__restrict__ cam_test,
-                                                      T *__restrict__ scal, int dst)
+                                                      T *__restrict__ scal, int dst, const unsigned short *__restrict__ cmask = nullptr)
 {
     __shared__ T red[4];
-    ba_retract_cams<T>(N, cam, dxc, gc, lam, cam_test, scal, dst, red);
+    ba_retract_cams<T, MASK>(N, cam, dxc, gc, lam, cam_test, scal, dst, red, cmask);
 }
 
 // ---- a-8: step control on the device ---------------------------------------------------------------------------

@@ -377,3 +377,37 @@ void ba_lm_params_default(ba_lm_params *p)
 }
 
 } // extern "C"
+
+int ba_problem_gauge_mask(const ba_problem *p, int ref_cam, unsigned short *cam_mask)
+{
+    if (!p || !cam_mask || p->N < 2 || ref_cam < 0 || ref_cam >= p->N) return BA_ERR_ARG;
+    // R T of camera a (the solver's initialisation: R = Rodrigues(omega)), its centre C = -R^T T
+    auto pose = [&](int a, double R[9], double T[3], double C[3]) {
+        const double *c = &p->cams9[9 * (size_t)a];
+        rodrigues(c, R);
+        for (int k = 0; k < 3; k++) T[k] = c[3 + k];
+        for (int k = 0; k < 3; k++) C[k] = -(R[k] * T[0] + R[3 + k] * T[1] + R[6 + k] * T[2]);
+    };
+    double Rr[9], Tr[3], Cr[3];
+    pose(ref_cam, Rr, Tr, Cr);
+    int b = -1;
+    double best = -1;
+    for (int a = 0; a < p->N; a++) {
+        if (a == ref_cam) continue;
+        double R[9], T[3], C[3];
+        pose(a, R, T, C);
+        const double d = (C[0] - Cr[0]) * (C[0] - Cr[0]) + (C[1] - Cr[1]) * (C[1] - Cr[1]) + (C[2] - Cr[2]) * (C[2] - Cr[2]);
+        if (d > best) { best = d; b = a; }
+    }
+    double R[9], T[3], C[3];
+    pose(b, R, T, C);
+    int k = 0;
+    double vmax = -1;
+    for (int q = 0; q < 3; q++) { // T_b + R_b C_ref = dT_b / ds under x -> C_ref + (1 + s)(x - C_ref)
+        const double v = std::fabs(T[q] + R[3 * q] * Cr[0] + R[3 * q + 1] * Cr[1] + R[3 * q + 2] * Cr[2]);
+        if (v > vmax) { vmax = v; k = q; }
+    }
+    cam_mask[ref_cam] |= (unsigned short)BA_FIX_POSE;
+    cam_mask[b] |= (unsigned short)(1u << k);
+    return BA_OK;
+}

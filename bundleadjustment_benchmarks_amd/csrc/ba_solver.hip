@@ -68,7 +68,12 @@ template <typename T> struct DevBuf {
         if (!h.empty() && hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return BA_ERR_HIP;
         return BA_OK;
     }
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+    }
+    ~DevBuf() { release(); }
 };
 
 struct SolverBase {
@@ -86,6 +91,7 @@ struct SolverBase {
     virtual int selftest(int which) = 0;
     virtual int set_pcg(int max_iter, double rel_tol) = 0;
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
+    virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
     virtual size_t device_bytes() const = 0;
     bool poisoned = false; // the watchdog gave up on a launch that never finished: every later call fails, nothing is freed
     int recoveries = 0;    // trials repeated through the launch-per-step factorisation after a hand-off time-out
@@ -525,11 +531,18 @@ template <typename T> struct Solver final : SolverBase {
         fa.eb = d_eb.p; // (nullptr when a point has more than 256 observations: plain runs of 256)
         fa.pt_ptr = d_pt_ptr.p; fa.lam = d_scal.p + SC_LAMBDA; fa.U0 = d_U0.p; fa.gp = d_gp.p;
         fa.rec = d_rec.p; fa.dinv = d_dinv.p; fa.tvec = d_tvec.p; fa.tri = d_tri.p; fa.fresh = &d_lm.p->rec_fresh;
+        fa.cmask = d_cmask.p; fa.pfix = d_pfix.p;
 #define BA_EVAL(J, F, ...) hipLaunchKernelGGL((k_eval<T, J, F, ##__VA_ARGS__>), dim3(gE), dim3(256), 0, st, Kl, N, Ml, d_cam[which].p, d_pts[which].p, d_obs_cam.p, d_obs_pt.p, \
                                          d_meas.p, tau2, d_r.p, d_Jc.p, d_Jp.p, d_JcA.p, d_part_e.p, go, commit ? d_cam[0].p : (T *)nullptr,              \
                                          commit ? d_pts[0].p : (T *)nullptr, fa)
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
+        // masked: the same launches through the instantiations that zero the fixed columns (ba_solver_set_constant)
         if (!jac) BA_EVAL(false, 0);
+        else if (masked) {
+            if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, true); else BA_EVAL(true, 0, false, true); }
+            else if (fused && fuse) BA_EVAL(true, 1, true, true);
+            else BA_EVAL(true, 0, true, true);
+        }
         else if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false); else BA_EVAL(true, 0, false); }
         else if (fused && fuse) BA_EVAL(true, 1);
         else BA_EVAL(true, 0);
@@ -561,6 +574,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         int rc;
         if ((rc = linearize_enqueue(diag_max != nullptr, nullptr))) return rc;
+        mask_pending = false; // (J, g and the records are now the current mask's)
         if (more_qr() && (rc = more_outer_finish(nullptr))) return rc;
         if (sharded()) { // the kernels left this shard's part in SC_ELOC (it also rides on the next trial's packed all-reduce)
             HIPCHK(hipMemcpyAsync(d_scal.p + SC_ENERGY, d_scal.p + SC_ELOC, sizeof(T), hipMemcpyDeviceToDevice, st));
@@ -952,7 +966,8 @@ template <typename T> struct Solver final : SolverBase {
                               &d_q1lam, &d_mQl, &d_mQR, &d_R22, &d_qB, &d_qAcopy, &d_dbgr, &d_dbg2, &d_stage, &d_pcg_M, &d_pcg_b, &d_pcg_r,
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
-        return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg);
+        return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
+               bytes_of(d_pfix);
     }
 
     int set_lambda(T lambda)
@@ -968,11 +983,66 @@ template <typename T> struct Solver final : SolverBase {
     {
         if (Ml > 0) { // the camera retraction rides as one more block at the end of the grid
             const ba_cam_retract_args cr{N, d_cam[0].p, d_dxc.p, d_gcg.p, d_cam[1].p, d_scal.p, (int)SC_RHO_C};
-            hipLaunchKernelGGL((k_backsub<T, 8>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
-                               d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr);
-        } else // (an empty shard keeps the zero partial sums written at creation)
+            // masked: the first reader of dx_c behind every kind's reduced solve forces the fixed rows (and fixed points) to a zero step
+            if (masked)
+                hipLaunchKernelGGL((k_backsub<T, 8, true>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
+                                   d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr,
+                                   ba_fix_args{d_cmask.p, d_pfix.p});
+            else
+                hipLaunchKernelGGL((k_backsub<T, 8>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
+                                   d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr);
+        } else if (masked) // (an empty shard keeps the zero partial sums written at creation)
+            hipLaunchKernelGGL((k_retract_cams<T, true>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
+                               d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)d_cmask.p);
+        else
             hipLaunchKernelGGL((k_retract_cams<T>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
                                d_cam[1].p, d_scal.p, (int)SC_RHO_C);
+    }
+
+    // ---- parameters held constant (ba_solver_set_constant) ---------------------------------------------------------------------------
+    // A mask with a bit set selects the masked instantiations of k_eval, k_backsub and k_retract_cams; nothing else changes (S, the
+    // records, J2bot and the reduced solves see zero columns).  No mask: no buffers, the kernels of a solver that never had one.
+    DevBuf<unsigned short> d_cmask; // [N]
+    DevBuf<unsigned char> d_pfix;   // [Ml] of this shard
+    bool masked = false;
+    bool mask_pending = false; // set since the last linearisation: J is the old mask's, try_step refuses
+    int set_constant(const unsigned short *cm, const unsigned char *pf) override
+    {
+        bool any = false, all = sx.M > 0 || N > 0;
+        for (int a = 0; cm && a < N; a++) {
+            const unsigned m = cm[a];
+            if (m & ~(unsigned)BA_FIX_CAMERA) return BA_ERR_ARG;                          // bits above 8
+            if ((m & BA_FIX_OMEGA) != 0 && (m & BA_FIX_OMEGA) != BA_FIX_OMEGA) return BA_ERR_ARG; // omega partly fixed
+            any = any || m != 0;
+            all = all && m == BA_FIX_CAMERA;
+        }
+        if (!cm) all = all && N == 0;
+        for (int j = 0; pf && j < sx.M; j++) {
+            any = any || pf[j] != 0;
+            all = all && pf[j] != 0;
+        }
+        if (!pf) all = all && sx.M == 0;
+        if (any && all) return BA_ERR_ARG; // nothing left to optimise
+        HIPCHK(hipStreamSynchronize(st));
+        if (!any) { d_cmask.release(); d_pfix.release(); }
+        else {
+            int rc;
+            std::vector<unsigned short> hc((size_t)N, 0);
+            std::vector<unsigned char> hp((size_t)(Ml > 0 ? Ml : 1), 0);
+            for (int a = 0; cm && a < N; a++) hc[a] = cm[a];
+            for (int j = 0; pf && j < Ml; j++) hp[j] = pf[sx.p0 + j] != 0;
+            if (!d_cmask.p && (rc = d_cmask.alloc(hc.size()))) return rc;
+            if (!d_pfix.p && (rc = d_pfix.alloc(hp.size()))) return rc;
+            HIPCHK(hipMemcpy(d_cmask.p, hc.data(), sizeof(unsigned short) * hc.size(), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_pfix.p, hp.data(), hp.size(), hipMemcpyHostToDevice));
+        }
+        masked = any;
+        // the captured iterations hold the other instantiations (and the buffers' addresses): captured again on the next ba_minimize
+        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl})
+            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        mask_pending = true;
+        have_step = false;
+        return BA_OK;
     }
 
     ba_red_jobs test_energy_jobs() const
@@ -1066,6 +1136,7 @@ template <typename T> struct Solver final : SolverBase {
     int try_step(double lambda_d, double *e_test, double *rho_scale, double *dx_norm) override
     {
         int rc;
+        if (mask_pending) return BA_ERR_ARG; // (the linearisation in place was made under another mask)
         if ((rc = set_lambda((T)lambda_d))) return rc;
         HIPCHK(hipEventRecord(ev[EV_T0], st));
         step_level = true;
@@ -1754,6 +1825,10 @@ int ba_solver_time_phase(ba_solver *s, int phase, int reps, double lambda, doubl
 int ba_solver_selftest(ba_solver *s, int which) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->selftest(which); }
 
 int ba_solver_set_pcg(ba_solver *s, int max_iter, double rel_tol) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_pcg(max_iter, rel_tol); }
+int ba_solver_set_constant(ba_solver *s, const unsigned short *cam_mask, const unsigned char *pt_fixed)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_constant(cam_mask, pt_fixed);
+}
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

@@ -287,6 +287,30 @@ int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset);
  * they exist). */
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes);
 
+/* ---- parameters held constant (no reference counterpart; Ceres' constant parameter blocks, g2o's fixed vertices) ------------------- */
+
+/* Bit q of a camera mask word = camera parameter q, in the order of the camera block of BA_GET_JC / BA_GET_DX / BA_GET_GRAD. */
+#define BA_FIX_T          0x007u /* T0 T1 T2 (bits 0..2, each on its own) */
+#define BA_FIX_OMEGA      0x038u /* w0 w1 w2 (bits 3..5, all three or none) */
+#define BA_FIX_POSE       0x03Fu
+#define BA_FIX_INTRINSICS 0x1C0u /* f k1 k2 (bits 6..8, each on its own) */
+#define BA_FIX_CAMERA     0x1FFu
+/* Removes the masked parameters from the optimisation, every kind, both scalar types, sharded or not: J's columns of a fixed parameter
+ * are zero (BA_GET_JC / BA_GET_JP / BA_GET_GRAD return zeros there; every other column is the unmasked solver's, bit for bit), and so is
+ * everything built from J -- S, rhs, lambda0 = 1e-12 max diag J'J, MOREQR's column norms, rho, the stop tests.  The damping stays
+ * lambda I (a fixed row of S is lambda alone; the reduced system keeps D = 9N).  The step of a fixed parameter is exactly 0 (BA_GET_DX)
+ * and its value keeps its bits through try_step, accept and ba_minimize (a camera whose omega is fixed keeps all 9 entries of R).
+ * cam_mask: N words (NULL = none); pt_fixed: M bytes of the PROBLEM, problem order, != 0 = the point's 3 coordinates fixed (NULL = none;
+ * a shard reads its own range [p0, p1)).  Masks that are NULL or all zero restore the unmasked path exactly.  The mask takes effect at
+ * the next ba_solver_linearize or ba_minimize; a ba_solver_try_step before that returns BA_ERR_ARG.  BA_ERR_ARG, the solver unchanged:
+ * bits above 8, omega partly fixed, every parameter fixed. */
+int ba_solver_set_constant(ba_solver *s, const unsigned short *cam_mask, const unsigned char *pt_fixed);
+/* Host only (no GPU): ORs into cam_mask (N words) a mask that fixes the 7-dimensional similarity gauge of J'J -- BA_FIX_POSE on camera
+ * ref_cam, and for the scale one component k of T_b of the camera b whose centre C_b = -R_b^T T_b lies farthest from C_ref (lowest index
+ * on a tie), k = argmax |(T_b + R_b C_ref)_k| (dT_b / ds under a scaling about C_ref; lowest k on a tie).  R = Rodrigues(omega) as the
+ * solver initialises it.  BA_ERR_ARG for N < 2 or ref_cam out of range. */
+int ba_problem_gauge_mask(const ba_problem *p, int ref_cam, unsigned short *cam_mask);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);

@@ -34,7 +34,9 @@ EXPORTS = [
     "ba_version", "ba_shard_plan", "ba_problem_save_cache", "ba_problem_load_cache", "ba_solver_selftest",
     "ba_comm_unique_id", "ba_comm_id_via_file", "ba_comm_id_file_done", "ba_solver_comm_init", "ba_solver_recoveries",
     "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes", "ba_solver_set_constant", "ba_problem_gauge_mask",
+    "ba_solver_covariance_compute", "ba_solver_covariance_get", "ba_solver_covariance_timing",
 ]
+ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
 
 class LMParams(C.Structure):
@@ -124,6 +126,9 @@ def lib():
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_constant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_problem_gauge_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.ba_solver_covariance_compute.argtypes = [C.c_void_p, C.c_double]
+        L.ba_solver_covariance_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ba_solver_covariance_timing.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -342,6 +347,32 @@ class Solver:
         st = PCGStats()
         _chk(lib().ba_solver_pcg_stats(self._h, C.byref(st), int(reset)), "ba_solver_pcg_stats")
         return {k: getattr(st, k) for k, _ in PCGStats._fields_}
+
+    def covariance(self, lam=0.0, cam_pairs=None, cams=None, points=None, compute=True):
+        """Covariance blocks of the estimate at the last linearize(): Sigma = (J'J + lam I)^-1 on the free parameters, 0 for fixed ones
+        (ba_solver_covariance_compute / _get; CHOLESKY and QRCHOL, F64, one shard).  cam_pairs: (n, 2) camera pairs -> (n, 9, 9);
+        cams=[a, ...] is shorthand for the diagonal pairs (a, a); points: point ids of the problem -> (m, 3, 3).  Returns
+        (camera blocks, point blocks), an empty array for a list not given.  compute=False reads further blocks of the last result.
+        Raises BAError: code ERR_SINGULAR when J'J + lam I is not positive definite on the free parameters."""
+        if cam_pairs is not None and cams is not None:
+            raise ValueError("give cam_pairs or cams, not both")
+        if cams is not None:
+            cams = np.asarray(cams, np.int32).reshape(-1)
+            cam_pairs = np.stack([cams, cams], axis=1)
+        pairs = np.zeros((0, 2), np.int32) if cam_pairs is None else np.ascontiguousarray(cam_pairs, np.int32).reshape(-1, 2)
+        pts = np.zeros(0, np.int32) if points is None else np.ascontiguousarray(points, np.int32).reshape(-1)
+        if compute:
+            _chk(lib().ba_solver_covariance_compute(self._h, float(lam)), "ba_solver_covariance_compute")
+        cc = np.empty((len(pairs), 9, 9))
+        pc = np.empty((len(pts), 3, 3))
+        _chk(lib().ba_solver_covariance_get(self._h, len(pairs), _p(pairs), _p(cc), len(pts), _p(pts), _p(pc)), "ba_solver_covariance_get")
+        return cc, pc
+
+    def covariance_timing(self):
+        """Device ms: (assembly, factorisation, inverse) of the last covariance compute, the point kernel of the last read of points."""
+        out = np.empty(4)
+        _chk(lib().ba_solver_covariance_timing(self._h, _p(out)), "ba_solver_covariance_timing")
+        return tuple(float(v) for v in out)
 
     def device_bytes(self):
         """Sum of the handle's device allocations."""

@@ -30,6 +30,7 @@ const char *ba_error_string(int err)
     case BA_ERR_HIP: return "HIP runtime error / no MI355X device";
     case BA_ERR_NOMEM: return "out of memory";
     case BA_ERR_COMM: return "communication (RCCL / all-reduce callback) failed";
+    case BA_ERR_SINGULAR: return "J'J + lambda I is not positive definite on the free parameters";
     }
     return "unknown error";
 }

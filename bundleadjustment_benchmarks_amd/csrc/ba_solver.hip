@@ -11,6 +11,7 @@
 #include "ba_dense.hip.h"
 #include "ba_qr.hip.h"
 #include "ba_pcg.hip.h"
+#include "ba_cov.hip.h"
 
 #include <chrono>
 #include <cmath>
@@ -21,6 +22,7 @@
 #include <numeric>
 #include <queue>
 #include <string>
+#include <type_traits>
 
 #define HIPCHK(x)                                                                                   \
     do {                                                                                            \
@@ -93,6 +95,9 @@ struct SolverBase {
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
     virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
     virtual size_t device_bytes() const = 0;
+    virtual int cov_compute(double lambda) = 0;
+    virtual int cov_get(int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov) = 0;
+    virtual int cov_timing(double *ms4) = 0;
     bool poisoned = false; // the watchdog gave up on a launch that never finished: every later call fails, nothing is freed
     int recoveries = 0;    // trials repeated through the launch-per-step factorisation after a hand-off time-out
     ba_allreduce_fn ar_fn = nullptr;
@@ -573,6 +578,7 @@ template <typename T> struct Solver final : SolverBase {
     int linearize(double *energy, double *diag_max) override
     {
         int rc;
+        cov_valid = false; // (a covariance is that of the linearisation it was computed from)
         if ((rc = linearize_enqueue(diag_max != nullptr, nullptr))) return rc;
         mask_pending = false; // (J, g and the records are now the current mask's)
         if (more_qr() && (rc = more_outer_finish(nullptr))) return rc;
@@ -587,6 +593,7 @@ template <typename T> struct Solver final : SolverBase {
         tm.n_linearize++;
         if (energy) *energy = (double)h_scal[SC_ENERGY];
         if (diag_max) *diag_max = std::max((double)h_scal[SC_DMAX_P], (double)h_scal[SC_DMAX_C]);
+        have_lin = true;
         return BA_OK;
     }
 
@@ -967,7 +974,138 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix);
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag);
+    }
+
+    // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
+    // The work buffer is the solver's only state of this feature: [C: cov_ld x (Dp + 64) | one panel Y: cov_ld x NB | the blocks'
+    // inverses W | the pivots (Dp) | the scaling (Dp) | the last trial's dx_c while the assembly borrows its buffer], allocated by the first compute.  The LM trial's own S, Wp, Winv and flags are not
+    // used by the factorisation here (S is assembled as a trial assembles it and then only read), x, xTest, J and the mask not at all.
+    DevBuf<T> d_cov;
+    DevBuf<int> d_cov_flag;
+    bool cov_valid = false; // a result that BA_GET-style reads may return: cleared by linearize / accept / set_state / set_constant / minimize
+    bool have_lin = false;  // a linearisation at x exists
+    double cov_lambda = 0, cov_ms[4] = {0, 0, 0, 0};
+    int cov_ld() const { return ((Dp + D + NAUG + NB - 1) / NB) * NB + 64; }
+    size_t cov_nmat() const { return (size_t)cov_ld() * (Dp + 64); }
+    T *cov_wp() const { return d_cov.p + cov_nmat(); }
+    T *cov_winv() const { return cov_wp() + (size_t)cov_ld() * NB; }
+    T *cov_dv() const { return cov_winv() + (size_t)((D + NB - 1) / NB) * NB * NB; }
+    T *cov_sc() const { return cov_dv() + Dp; }
+    T *cov_dxsave() const { return cov_sc() + Dp; }
+    size_t cov_count() const { return cov_nmat() + (size_t)cov_ld() * NB + (size_t)((D + NB - 1) / NB) * NB * NB + 2 * (size_t)Dp + d_dxc.n; }
+
+    int cov_compute(double lambda) override
+    {
+        if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG; // (a single-precision inverse at these condition numbers is noise)
+        else {
+            // refusals: host side, before any launch
+            if ((kind != BA_CHOLESKY && kind != BA_QRCHOL) || sharded() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda))
+                return BA_ERR_ARG;
+            cov_valid = false;
+            int rc;
+            if (!d_cov.p) {
+                if ((rc = d_cov.alloc(cov_count())) || (rc = d_cov_flag.alloc(1))) {
+                    (void)hipGetLastError(); // (the solver stays usable)
+                    d_cov.release(); d_cov_flag.release();
+                    return rc;
+                }
+            }
+            const int ldc = cov_ld();
+            int flag = 0;
+            HIPCHK(hipMemsetAsync(d_cov_flag.p, 0, sizeof(int), st));
+            if ((rc = set_lambda((T)lambda))) return rc;
+            HIPCHK(hipEventRecord(ev[EV_T0], st));
+            // S(lambda) as a trial assembles it (segment A + the diagonal's lambda), left unfactored in d_S.  The assembly arms the back
+            // sweep's hand-over vector, which is where the last trial's dx_c lives (BA_GET_DX): kept aside and put back.
+            HIPCHK(hipMemcpyAsync(cov_dxsave(), d_dxc.p, sizeof(T) * d_dxc.n, hipMemcpyDeviceToDevice, st));
+            launch_eliminate();
+            if (masked && d_pfix.p) // (a fixed point's U_p = lambda I is never inverted: its records are the zeros they stand for)
+                hipLaunchKernelGGL((k_cov_fixed_records<T>), dim3((std::max(Kl, Ml) + 255) / 256), dim3(256), 0, st, Kl, Ml, (int)BA_REC, (const int *)d_obs_pt.p,
+                                   (const unsigned char *)d_pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
+            launch_schur();
+            launch_post_reduce();
+            HIPCHK(hipMemcpyAsync(d_dxc.p, cov_dxsave(), sizeof(T) * d_dxc.n, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemsetAsync(d_cov.p, 0, sizeof(T) * cov_nmat(), st));
+            hipLaunchKernelGGL((k_cov_scale<T>), dim3((D + 255) / 256), dim3(256), 0, st, D, ld, (const T *)d_S.p, (const unsigned short *)d_cmask.p,
+                               cov_sc(), d_cov_flag.p);
+            hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
+                               (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), d_cov_flag.p);
+            hipLaunchKernelGGL((k_cov_stage<T>), dim3(((D + NB - 1) / NB) * NB), dim3(256), 0, st, D, Dp, ld, (const T *)d_S.p, (const T *)cov_sc(), ldc, d_cov.p);
+            HIPCHK(hipEventRecord(ev[EV_T1], st));
+            HIPCHK(hipMemcpyAsync(&flag, d_cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (flag) return BA_ERR_SINGULAR; // a free parameter nobody observes: nothing is factored
+            // launch-per-step factorisation (no workgroup waits for another one) with the stacked rows riding along
+            ba_ldlt_factor<T, NB>(st, Dp + D, ((D + NB - 1) / NB) * NB /* the last block column padded with unit pivots */, ldc, d_cov.p, cov_wp(), cov_winv(), (int *)nullptr, 0, (T *)nullptr, /*safe*/ true, 0);
+            HIPCHK(hipEventRecord(ev[EV_T2], st));
+            hipLaunchKernelGGL((k_cov_diag<T>), dim3((Dp + 255) / 256), dim3(256), 0, st, D, Dp, ldc, (const T *)d_cov.p, (const T *)cov_sc(), cov_dv(), d_cov_flag.p);
+            const int nt = (D + 63) / 64;
+            hipLaunchKernelGGL((k_cov_syrk<T>), dim3(nt * (nt + 1) / 2), dim3(256), 0, st, D, Dp, ldc, d_cov.p, (const T *)cov_dv());
+            HIPCHK(hipEventRecord(ev[EV_T3], st));
+            HIPCHK(hipMemcpyAsync(&flag, d_cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            cov_ms[0] = ev_ms(EV_T0, EV_T1); cov_ms[1] = ev_ms(EV_T1, EV_T2); cov_ms[2] = ev_ms(EV_T2, EV_T3);
+            if (flag) return BA_ERR_SINGULAR; // a pivot <= 0 (or not finite): no result is left behind
+            cov_lambda = lambda;
+            cov_valid = true;
+            return BA_OK;
+        }
+    }
+
+    int cov_get(int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov) override
+    {
+        if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG;
+        else {
+            if (!cov_valid || n_pairs < 0 || n_pts < 0 || (n_pairs > 0 && (!cam_pairs || !cam_cov)) || (n_pts > 0 && (!pt_ids || !pt_cov))) return BA_ERR_ARG;
+            for (int q = 0; q < 2 * n_pairs; q++)
+                if (cam_pairs[q] < 0 || cam_pairs[q] >= N) return BA_ERR_ARG;
+            for (int q = 0; q < n_pts; q++)
+                if (pt_ids[q] < 0 || pt_ids[q] >= Ml) return BA_ERR_ARG; // (single shard: the shard's points are the problem's)
+            const int ldc = cov_ld();
+            int rc;
+            HIPCHK(hipStreamSynchronize(st));
+            if (n_pairs > 0) {
+                DevBuf<int> d_idx;
+                DevBuf<double> d_out;
+                if ((rc = d_idx.alloc((size_t)2 * n_pairs)) || (rc = d_out.alloc((size_t)81 * n_pairs))) { (void)hipGetLastError(); return rc; }
+                HIPCHK(hipMemcpy(d_idx.p, cam_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
+                hipLaunchKernelGGL((k_cov_get_cams<T>), dim3((unsigned)(((size_t)81 * n_pairs + 255) / 256)), dim3(256), 0, st, n_pairs, (const int *)d_idx.p, ldc,
+                                   (const T *)d_cov.p, (const unsigned short *)d_cmask.p, d_out.p);
+                HIPCHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpy(cam_cov, d_out.p, sizeof(double) * 81 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+            }
+            if (n_pts > 0) {
+                DevBuf<int> d_idx;
+                DevBuf<double> d_out;
+                if ((rc = d_idx.alloc((size_t)n_pts)) || (rc = d_out.alloc((size_t)9 * n_pts))) { (void)hipGetLastError(); return rc; }
+                HIPCHK(hipMemcpy(d_idx.p, pt_ids, sizeof(int) * (size_t)n_pts, hipMemcpyHostToDevice));
+                // J of the linearisation, not the elimination's records: those are a later trial's by now
+                HIPCHK(hipEventRecord(ev[EV_T4], st));
+                if (chol_elim())
+                    hipLaunchKernelGGL((k_cov_points<T, true>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
+                                       (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
+                                       (const T *)d_cov.p, d_out.p);
+                else
+                    hipLaunchKernelGGL((k_cov_points<T, false>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
+                                       (const int *)d_obs_cam.p, (const T *)d_Jc.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
+                                       (const T *)d_cov.p, d_out.p);
+                HIPCHK(hipEventRecord(ev[EV_T5], st));
+                HIPCHK(hipStreamSynchronize(st));
+                cov_ms[3] = ev_ms(EV_T4, EV_T5);
+                HIPCHK(hipMemcpy(pt_cov, d_out.p, sizeof(double) * 9 * (size_t)n_pts, hipMemcpyDeviceToHost));
+            }
+            HIPCHK(hipGetLastError());
+            return BA_OK;
+        }
+    }
+    // ms of the last compute: assembly (elimination, S, staging) | factorisation | inverse (pivots + rank-D update); of the last get
+    // with points: the point kernel
+    int cov_timing(double *ms4) override
+    {
+        for (int q = 0; q < 4; q++) ms4[q] = cov_ms[q];
+        return BA_OK;
     }
 
     int set_lambda(T lambda)
@@ -1024,6 +1162,7 @@ template <typename T> struct Solver final : SolverBase {
         if (!pf) all = all && sx.M == 0;
         if (any && all) return BA_ERR_ARG; // nothing left to optimise
         HIPCHK(hipStreamSynchronize(st));
+        cov_valid = false;
         if (!any) { d_cmask.release(); d_pfix.release(); }
         else {
             int rc;
@@ -1166,6 +1305,7 @@ template <typename T> struct Solver final : SolverBase {
     int accept() override
     {
         if (!have_step) return BA_ERR_ARG;
+        cov_valid = false;
         const int ncam = 15 * N, npts = 3 * Ml;
         hipLaunchKernelGGL((k_commit<T>), dim3((ncam + npts + 255) / 256), dim3(256), 0, st, ncam, npts, d_cam[1].p, d_pts[1].p, d_cam[0].p, d_pts[0].p,
                            (const int *)nullptr);
@@ -1341,6 +1481,8 @@ template <typename T> struct Solver final : SolverBase {
     int set_state(const double *cam15, const double *pts) override
     {
         HIPCHK(hipStreamSynchronize(st));
+        cov_valid = false;
+        have_lin = false; // (J is another state's)
         if (cam15) {
             std::vector<T> h((size_t)15 * N);
             for (int a = 0; a < N; a++)
@@ -1596,6 +1738,8 @@ template <typename T> struct Solver final : SolverBase {
         }
         if (talk) printf("--------------------------------------------------------------------------------\n");
         have_step = false;
+        cov_valid = false;
+        have_lin = false; // (ba_solver_covariance_compute wants a ba_solver_linearize at the final x first)
         if (out) {
             out->status = h.status; out->iterations = h.iter; out->trials = h.trials; out->fun_evals = h.fun_evals;
             out->energy = (double)h.energy; out->lambda = (double)h.lambda;
@@ -1836,5 +1980,11 @@ int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
     *bytes = s->impl->device_bytes();
     return BA_OK;
 }
+int ba_solver_covariance_compute(ba_solver *s, double lambda) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->cov_compute(lambda); }
+int ba_solver_covariance_get(ba_solver *s, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->cov_get(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov);
+}
+int ba_solver_covariance_timing(ba_solver *s, double *ms4) { return !(s && ms4) ? BA_ERR_ARG : s->impl->cov_timing(ms4); }
 
 } // extern "C"

@@ -31,7 +31,8 @@ enum {
     BA_ERR_ARG = 4,
     BA_ERR_HIP = 5,   /* HIP runtime error or no gfx950 device: the product path never falls back to a CPU */
     BA_ERR_NOMEM = 6,
-    BA_ERR_COMM = 7
+    BA_ERR_COMM = 7,
+    BA_ERR_SINGULAR = 8 /* ba_solver_covariance_compute: J'J + lambda I is not positive definite on the free parameters */
 };
 
 /* Solver symbols of the reference build (src/CMakeLists.txt:95-178; src/Optimization/BAFunctor.h:98-117).
@@ -310,6 +311,36 @@ int ba_solver_set_constant(ba_solver *s, const unsigned short *cam_mask, const u
  * on a tie), k = argmax |(T_b + R_b C_ref)_k| (dT_b / ds under a scaling about C_ref; lowest k on a tie).  R = Rodrigues(omega) as the
  * solver initialises it.  BA_ERR_ARG for N < 2 or ref_cam out of range. */
 int ba_problem_gauge_mask(const ba_problem *p, int ref_cam, unsigned short *cam_mask);
+
+/* ---- covariance blocks (no reference counterpart; Ceres' Covariance, g2o's computeMarginals) ---------------------------------------- */
+
+/* With J the Jacobian of the last ba_solver_linearize (robustified residuals, masked columns zero), F the set of free parameters and
+ * H = (J'J + lambda I) restricted to F:   Sigma = H^-1 on F x F, exactly 0 in every row and column of a fixed parameter.
+ * Sigma is the covariance of the estimate in the solver's own tangent parametrisation (camera block in the order of BA_GET_DX: T, omega,
+ * f, k1, k2; point block x, y, z) for unit variance of the robustified residuals; scaling by a sigma^2 is the caller's.  lambda = 0 is
+ * the meaningful value once the gauge is fixed (ba_problem_gauge_mask); lambda > 0 gives the damped inverse.
+ * compute: assembles S(lambda) from the current linearisation as a trial does, factors the symmetrically scaled matrix
+ * diag(S)^-1/2 S diag(S)^-1/2 (fixed rows: unit diagonal) by the dense LDL^T with the scaling stacked below it, and forms the inverse
+ * of the free block on the device.  BA_CHOLESKY and BA_QRCHOL, BA_F64, shard_world == 1; anything else BA_ERR_ARG, as are lambda < 0 or
+ * not finite, no ba_solver_linearize since creation / ba_solver_set_state / ba_minimize, and a mask set since the last linearisation.
+ * BA_ERR_SINGULAR, no result left behind: a pivot <= 0 of S or of a free point's 3 x 3 block (lambda = 0 without a gauge mask, a
+ * parameter nobody observes) -- found on the device, a flag word read back with the call.  x, xTest, the linearisation and the mask are
+ * untouched: a ba_solver_try_step or ba_minimize behind it returns the bits it returns without it, and behind a ba_solver_try_step the
+ * step (BA_GET_DX), the kept S / rhs (BA_GET_S, BA_GET_RHS), xTest and ba_solver_accept are what they were.  What a compute does spend
+ * is internal: the last trial's elimination records and the factored S, which every trial rebuilds.
+ * Memory: one buffer of its own, allocated by the first compute, counted by ba_solver_device_bytes, released by ba_solver_free:
+ *   8 (ldc (Dp + 128) + 4096 ceil(D / 64) + 4 Dp + 128) + 4 bytes,  D = 9 N, Dp = 64 ceil((D + 3) / 64), ldc = 64 ceil((Dp + D + 3) / 64) + 64
+ * (the inverse rides the factorisation as D extra rows: ~2 D x D scalars).  BA_ERR_NOMEM when it does not fit, the solver stays usable. */
+int ba_solver_covariance_compute(ba_solver *s, double lambda);
+/* Blocks of the last computed covariance.  cam_pairs: n_pairs x (a, b) -> 81 doubles each, row-major block Sigma_ab (Sigma_ba is its
+ * transpose bit for bit); pt_ids: n_pts points in the PROBLEM's numbering -> 9 doubles each, computed on the device for these points
+ * only (O(t^2) 9 x 9 blocks for a track of t observations).  Either list may be empty.  BA_ERR_ARG: no successful compute yet, or a
+ * ba_solver_linearize / ba_solver_accept / ba_solver_set_state / ba_solver_set_constant / ba_minimize since (the result is stale), an
+ * index out of range.  A ba_solver_try_step in between does not invalidate the result. */
+int ba_solver_covariance_get(ba_solver *s, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov);
+/* Device ms (HIP events): ms4 = {elimination + assembly of S + staging, factorisation, inverse from the factor} of the last compute and
+ * the point kernel of the last ba_solver_covariance_get that asked for points. */
+int ba_solver_covariance_timing(ba_solver *s, double *ms4);
 
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);

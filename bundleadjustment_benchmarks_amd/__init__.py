@@ -22,6 +22,9 @@ STATUS = {-2: "NotStarted", -1: "Running", 0: "Success", 1: "ExceededLambdaMax",
 # ba_solver_set_constant: bit q of a camera's mask word = camera parameter q (the camera block of GET_JC / GET_DX / GET_GRAD)
 FIX_T, FIX_OMEGA, FIX_POSE, FIX_INTRINSICS, FIX_CAMERA = 0x007, 0x038, 0x03F, 0x1C0, 0x1FF
 
+# ba_solver_set_loss: rho(s) of the weighted squared reprojection error s (include/ba_mi355x.h); a new solver is (LOSS_REFERENCE, 0.5)
+LOSS_REFERENCE, LOSS_TRIVIAL, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2, 3
+
 (GET_RESIDUALS, GET_JC, GET_JP, GET_GRAD, GET_S, GET_RHS, GET_DX, GET_CAMS, GET_POINTS, GET_CAMS_TEST,
  GET_POINTS_TEST) = range(11)
 
@@ -35,6 +38,7 @@ EXPORTS = [
     "ba_comm_unique_id", "ba_comm_id_via_file", "ba_comm_id_file_done", "ba_solver_comm_init", "ba_solver_recoveries",
     "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes", "ba_solver_set_constant", "ba_problem_gauge_mask",
     "ba_solver_covariance_compute", "ba_solver_covariance_get", "ba_solver_covariance_timing",
+    "ba_solver_set_loss", "ba_solver_set_obs_weights",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -129,6 +133,8 @@ def lib():
         L.ba_solver_covariance_compute.argtypes = [C.c_void_p, C.c_double]
         L.ba_solver_covariance_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ba_solver_covariance_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.ba_solver_set_obs_weights.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -341,6 +347,20 @@ class Solver:
                 raise ValueError("pt_fixed must be a bool or uint8 array of shape (%d,), got %s %s" % (M, pt_fixed.dtype, pt_fixed.shape))
             pt_fixed = np.ascontiguousarray(pt_fixed.astype(np.uint8))
         _chk(lib().ba_solver_set_constant(self._h, _p(cam_mask), _p(pt_fixed)), "ba_solver_set_constant")
+
+    def set_loss(self, kind, scale=0.5):
+        """Loss of the measurement model from the next linearize() / minimize() on: LOSS_REFERENCE (scale = tau; the default is tau = 0.5),
+        LOSS_TRIVIAL (scale ignored), LOSS_HUBER (scale = delta), LOSS_CAUCHY (scale = c)."""
+        _chk(lib().ba_solver_set_loss(self._h, int(kind), float(scale)), "ba_solver_set_loss")
+
+    def set_obs_weights(self, w=None):
+        """Per-observation weights w_o > 0 of the residual r_o = w_o (projection - measurement), e.g. 1 / sigma_o: K of the problem, in
+        the order of the input file (None: no weights).  Takes effect at the next linearize() / minimize()."""
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64)
+            if w.shape != (self.problem.K,):
+                raise ValueError("w must have shape (%d,), got %s" % (self.problem.K, w.shape))
+        _chk(lib().ba_solver_set_obs_weights(self._h, _p(w)), "ba_solver_set_obs_weights")
 
     def pcg_stats(self, reset=False):
         """ITERSCHUR: solves and iterations counted on the device; the last solve's iterations, convergence and |rhs - S dx_c| / |rhs|."""

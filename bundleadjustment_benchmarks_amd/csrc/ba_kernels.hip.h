@@ -156,13 +156,61 @@ template <typename T> struct ba_fuse_args {
     int *fresh;
     const unsigned short *cmask; // MASK: per camera, bit q = camera column q held constant (ba_solver_set_constant)
     const unsigned char *pfix;   // MASK: per point of the shard, != 0 = its three columns held constant
+    const T *wobs;               // MODEL: per observation of the shard (solver order), its weight; nullptr = all 1
+    int loss;                    // MODEL: ba_loss_kind (wave-uniform)
+    T lscale;                    // MODEL: the loss's scale (tau / delta / c); its square travels in k_eval's tau2
 };
 // SOA = false (CHOLESKY): the camera blocks are kept in the AoS records JcA alone -- k_cam_gram gathers them by camera, k_elim_chol reads
 // its own record -- and the 18 SoA streams Jc (144 of the 624 bytes this kernel writes per observation when fused) are not written.
+// MODEL (ba_solver_set_loss / ba_solver_set_obs_weights): the general measurement model.  r = w (pi - meas), s = |r|^2, and the
+// robustified residual e = g r with g = sqrt(rho(s) / s), whose full derivative is
+//   de/dr = g (I - rh rh') + (rho' sqrt(s) / sqrt(rho)) rh rh' = g I + ((rho' - rho / s) / g) rh rh',   rh = r / sqrt(s)
+// (the chain rule of the lines below for rho = psi, rho' = W / 2).  ba_loss returns g and q = (rho' - rho / s) / g from closed forms of
+// rho / s that are finite at s = 0 (g -> sqrt(rho'(0)), q -> 0): nothing is divided by s below a kink.  The default model
+// (BA_LOSS_REFERENCE at 0.5 px without weights) never comes here: MODEL = false is the kernel as it was, the reference's clamps at
+// |r| -> 0 included.
+#define BA_LOSS_K_REFERENCE 0
+#define BA_LOSS_K_TRIVIAL 1
+#define BA_LOSS_K_HUBER 2
+#define BA_LOSS_K_CAUCHY 3
+__device__ __forceinline__ double tlog1p(double x) { return log1p(x); }
+__device__ __forceinline__ float tlog1p(float x) { return log1pf(x); }
+template <typename T> __device__ __forceinline__ void ba_loss(int kind, T s, T sc, T sc2, T &g, T &q)
+{
+    g = (T)1.0; q = (T)0; // BA_LOSS_TRIVIAL, and Huber's quadratic part exactly
+    if (kind == BA_LOSS_K_REFERENCE) { // psi (BAFunctor.h:147): s (2 - s / tau^2) / 4 below tau^2, tau^2 / 4 above
+        if (s < sc2) {
+            const T h = (T)0.25 * (s / sc2);
+            g = tsqrt((T)0.5 - h);
+            q = -h / g;
+        } else {
+            g = (T)0.5 * sc / tsqrt(s); // rho / s = tau^2 / (4 s), rho' = 0
+            q = -g;
+        }
+    } else if (kind == BA_LOSS_K_HUBER) { // s below delta^2, 2 delta sqrt(s) - delta^2 above
+        if (s > sc2) {
+            const T n = tsqrt(s);
+            g = tsqrt(sc * (n + (n - sc))) / n;
+            q = -sc * (n - sc) / (s * g); // rho' - rho / s = delta / sqrt(s) - (2 delta sqrt(s) - delta^2) / s
+        }
+    } else if (kind == BA_LOSS_K_CAUCHY) { // c^2 log(1 + s / c^2)
+        const T u = s / sc2;
+        T phi, d; // rho / s = log1p(u) / u, rho' - rho / s: by their series where u is small (0 / 0 at u = 0)
+        if (u < (T)1e-3) {
+            phi = (T)1.0 - u * ((T)(1.0 / 2) - u * ((T)(1.0 / 3) - u * ((T)(1.0 / 4) - u * ((T)(1.0 / 5) - u * (T)(1.0 / 6)))));
+            d = -u * ((T)(1.0 / 2) - u * ((T)(2.0 / 3) - u * ((T)(3.0 / 4) - u * ((T)(4.0 / 5) - u * (T)(5.0 / 6)))));
+        } else {
+            phi = tlog1p(u) / u;
+            d = (T)1.0 / ((T)1.0 + u) - phi;
+        }
+        g = tsqrt(phi);
+        q = d / g;
+    }
+}
 // MASK (ba_solver_set_constant): the columns of the parameters held constant are written as zeros -- Jc, JcA, Jp and the fused Aj / Bj
 // alike, so that everything built from J (g, U, V, S, the records, J2bot, max diag J'J) is the masked J's.  A separate instantiation:
 // the unmasked launch stays the kernel it was.
-template <typename T, bool JAC, int FUSE = 0, bool SOA = true, bool MASK = false>
+template <typename T, bool JAC, int FUSE = 0, bool SOA = true, bool MASK = false, bool MODEL = false>
 __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__restrict__ cam, const T *__restrict__ pts,
                                               const int *__restrict__ obs_cam, const int *__restrict__ obs_pt,
                                               const T *__restrict__ meas, T tau2, T *__restrict__ r, T *__restrict__ Jc,
@@ -207,14 +255,22 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
         const T f = c[12], k1 = c[13], k2 = c[14];
         const T kr = 1 + k1 * r2u + k2 * r4u;
         const T xd0 = kr * xu0, xd1 = kr * xu1;
-        const T r0 = f * xd0 - meas[i], r1 = f * xd1 - meas[(size_t)K + i];
+        const T wo = (MODEL && fa.wobs) ? fa.wobs[i] : (T)1.0;
+        const T r0 = MODEL ? wo * (f * xd0 - meas[i]) : f * xd0 - meas[i];
+        const T r1 = MODEL ? wo * (f * xd1 - meas[(size_t)K + i]) : f * xd1 - meas[(size_t)K + i];
         const T r2 = r0 * r0 + r1 * r1;
-        // psi (BAFunctor.h:147)
-        const T psi = (r2 < tau2) ? r2 * ((T)2.0 - r2 / tau2) / (T)4.0 : tau2 / (T)4.0;
-        const T sqrt_psi = tsqrt(psi);
-        const T nr = tsqrt(r2);
-        const T rnorm_r = (T)1.0 / tmax((T)BA_EPS_PSI, nr);
-        const T e0 = r0 * sqrt_psi * rnorm_r, e1 = r1 * sqrt_psi * rnorm_r;
+        T e0, e1, sqrt_psi = 0, nr = 0, rnorm_r = 0, lg = 0, lq = 0;
+        if constexpr (MODEL) {
+            ba_loss<T>(fa.loss, r2, fa.lscale, tau2, lg, lq);
+            e0 = lg * r0; e1 = lg * r1;
+        } else {
+            // psi (BAFunctor.h:147)
+            const T psi = (r2 < tau2) ? r2 * ((T)2.0 - r2 / tau2) / (T)4.0 : tau2 / (T)4.0;
+            sqrt_psi = tsqrt(psi);
+            nr = tsqrt(r2);
+            rnorm_r = (T)1.0 / tmax((T)BA_EPS_PSI, nr);
+            e0 = r0 * sqrt_psi * rnorm_r; e1 = r1 * sqrt_psi * rnorm_r;
+        }
         e2 = e0 * e0 + e1 * e1;
         if (JAC) {
             ej[0] = e0; ej[1] = e1;
@@ -233,15 +289,24 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
             dpX[0] = p00 * a00; dpX[1] = p01 * a00; dpX[2] = p00 * a02 + p01 * a12;
             dpX[3] = p01 * a00; dpX[4] = p11 * a00; dpX[5] = p01 * a02 + p11 * a12;
             // outer derivative of the robustified residual (BAFunctor.h:227-242)
-            const T tw = (T)1.0 - r2 / tau2;
-            const T W = tw > (T)0 ? tw : (T)0;
-            const T rsqrt_psi = (T)1.0 / tmax((T)BA_EPS_PSI, sqrt_psi);
-            const T rcp_r2 = (T)1.0 / tmax((T)BA_EPS_PSI, r2);
-            const T rr00 = r0 * r0 * rnorm_r, rr01 = r0 * r1 * rnorm_r, rr11 = r1 * r1 * rnorm_r;
-            const T c1 = W / (T)2.0 * rsqrt_psi, c2 = sqrt_psi * rcp_r2;
-            const T o00 = c1 * rr00 + c2 * (nr - rr00);
-            const T o01 = c1 * rr01 + c2 * ((T)0 - rr01);
-            const T o11 = c1 * rr11 + c2 * (nr - rr11);
+            T o00, o01, o11;
+            if constexpr (MODEL) { // (de/dr) w: g I + q rh rh', the weight of r = w (pi - meas) folded in
+                const T rn = (T)1.0 / tmax((T)BA_EPS_PSI, tsqrt(r2));
+                const T h0 = r0 * rn, h1 = r1 * rn, qw = lq * wo, gw = lg * wo;
+                o00 = gw + qw * (h0 * h0);
+                o01 = qw * (h0 * h1);
+                o11 = gw + qw * (h1 * h1);
+            } else {
+                const T tw = (T)1.0 - r2 / tau2;
+                const T W = tw > (T)0 ? tw : (T)0;
+                const T rsqrt_psi = (T)1.0 / tmax((T)BA_EPS_PSI, sqrt_psi);
+                const T rcp_r2 = (T)1.0 / tmax((T)BA_EPS_PSI, r2);
+                const T rr00 = r0 * r0 * rnorm_r, rr01 = r0 * r1 * rnorm_r, rr11 = r1 * r1 * rnorm_r;
+                const T c1 = W / (T)2.0 * rsqrt_psi, c2 = sqrt_psi * rcp_r2;
+                o00 = c1 * rr00 + c2 * (nr - rr00);
+                o01 = c1 * rr01 + c2 * ((T)0 - rr01);
+                o11 = c1 * rr11 + c2 * (nr - rr11);
+            }
             T Jb[24];
 #pragma unroll
             for (int rr = 0; rr < 2; rr++) {

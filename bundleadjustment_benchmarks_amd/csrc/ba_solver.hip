@@ -94,6 +94,8 @@ struct SolverBase {
     virtual int set_pcg(int max_iter, double rel_tol) = 0;
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
     virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
+    virtual int set_loss(int kind, double scale) = 0;
+    virtual int set_obs_weights(const double *w) = 0;
     virtual size_t device_bytes() const = 0;
     virtual int cov_compute(double lambda) = 0;
     virtual int cov_get(int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov) = 0;
@@ -531,18 +533,32 @@ template <typename T> struct Solver final : SolverBase {
     // fused (with jac): the point part of the gradient and, CHOLESKY, the next trial's elimination in the same pass (k_eval<T, true, FUSE>)
     void launch_eval(bool jac, int which, const int *go = nullptr, bool commit = false, bool fused = false)
     {
-        const T tau2 = tau * tau;
+        const T tau2 = loss_scale * loss_scale; // (the square of the loss's scale: tau^2 of the reference's psi by default)
         ba_fuse_args<T> fa{};
         fa.eb = d_eb.p; // (nullptr when a point has more than 256 observations: plain runs of 256)
         fa.pt_ptr = d_pt_ptr.p; fa.lam = d_scal.p + SC_LAMBDA; fa.U0 = d_U0.p; fa.gp = d_gp.p;
         fa.rec = d_rec.p; fa.dinv = d_dinv.p; fa.tvec = d_tvec.p; fa.tri = d_tri.p; fa.fresh = &d_lm.p->rec_fresh;
         fa.cmask = d_cmask.p; fa.pfix = d_pfix.p;
+        fa.wobs = d_wobs.p; fa.loss = loss_kind; fa.lscale = loss_scale;
 #define BA_EVAL(J, F, ...) hipLaunchKernelGGL((k_eval<T, J, F, ##__VA_ARGS__>), dim3(gE), dim3(256), 0, st, Kl, N, Ml, d_cam[which].p, d_pts[which].p, d_obs_cam.p, d_obs_pt.p, \
                                          d_meas.p, tau2, d_r.p, d_Jc.p, d_Jp.p, d_JcA.p, d_part_e.p, go, commit ? d_cam[0].p : (T *)nullptr,              \
                                          commit ? d_pts[0].p : (T *)nullptr, fa)
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
         // masked: the same launches through the instantiations that zero the fixed columns (ba_solver_set_constant)
-        if (!jac) BA_EVAL(false, 0);
+        // model(): the same launches again through the instantiations of the general measurement model (ba_solver_set_loss /
+        // ba_solver_set_obs_weights); the reference's psi at 0.5 px without weights stays on the kernels it always ran
+        if (model()) {
+            if (!jac) BA_EVAL(false, 0, true, false, true);
+            else if (masked) {
+                if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, true, true); else BA_EVAL(true, 0, false, true, true); }
+                else if (fused && fuse) BA_EVAL(true, 1, true, true, true);
+                else BA_EVAL(true, 0, true, true, true);
+            }
+            else if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, false, true); else BA_EVAL(true, 0, false, false, true); }
+            else if (fused && fuse) BA_EVAL(true, 1, true, false, true);
+            else BA_EVAL(true, 0, true, false, true);
+        }
+        else if (!jac) BA_EVAL(false, 0);
         else if (masked) {
             if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, true); else BA_EVAL(true, 0, false, true); }
             else if (fused && fuse) BA_EVAL(true, 1, true, true);
@@ -974,7 +990,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag);
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs);
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1143,7 +1159,7 @@ template <typename T> struct Solver final : SolverBase {
     DevBuf<unsigned short> d_cmask; // [N]
     DevBuf<unsigned char> d_pfix;   // [Ml] of this shard
     bool masked = false;
-    bool mask_pending = false; // set since the last linearisation: J is the old mask's, try_step refuses
+    bool mask_pending = false; // a mask or a measurement model set since the last linearisation: J is the old one's, try_step refuses
     int set_constant(const unsigned short *cm, const unsigned char *pf) override
     {
         bool any = false, all = sx.M > 0 || N > 0;
@@ -1182,6 +1198,50 @@ template <typename T> struct Solver final : SolverBase {
         mask_pending = true;
         have_step = false;
         return BA_OK;
+    }
+
+    // ---- measurement model (ba_solver_set_loss / ba_solver_set_obs_weights) -----------------------------------------------------------
+    // Anything but the reference's psi at its 0.5 px without weights selects the MODEL instantiations of k_eval; nothing else changes
+    // (everything downstream is built from e and J).  psi at another tau goes there too: the default kernels keep the reference's
+    // clamps 1 / max(1e-15, .), which falsify dE/dr below |r|^2 = 1e-15, and the model's contract is a derivative that is right down to 0.  `tau` stays the reference's threshold: ba_solver_stats is its only other consumer.
+    int loss_kind = BA_LOSS_REFERENCE;
+    T loss_scale = (T)0.5;
+    DevBuf<T> d_wobs; // [Kl] of this shard, the solver's observation order (like d_meas)
+    bool model() const { return loss_kind != BA_LOSS_REFERENCE || loss_scale != (T)0.5 || d_wobs.p != nullptr; }
+    // the captured iterations hold the other instantiations and kernel arguments: captured again on the next ba_minimize
+    int model_changed()
+    {
+        cov_valid = false;
+        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl})
+            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        mask_pending = true;
+        have_step = false;
+        return BA_OK;
+    }
+    int set_loss(int kind, double scale) override
+    {
+        if (kind < BA_LOSS_REFERENCE || kind > BA_LOSS_CAUCHY) return BA_ERR_ARG;
+        if (kind == BA_LOSS_TRIVIAL) scale = 1.0; // (ignored)
+        else if (!(scale > 0) || !std::isfinite(scale) || !((T)scale > 0) || !std::isfinite((T)scale)) return BA_ERR_ARG;
+        HIPCHK(hipStreamSynchronize(st));
+        loss_kind = kind;
+        loss_scale = (T)scale;
+        return model_changed();
+    }
+    int set_obs_weights(const double *w) override
+    {
+        for (int i = 0; w && i < sx.K; i++)
+            if (!(w[i] > 0) || !std::isfinite(w[i]) || !((T)w[i] > 0) || !std::isfinite((T)w[i])) return BA_ERR_ARG;
+        HIPCHK(hipStreamSynchronize(st));
+        if (!w) d_wobs.release();
+        else {
+            std::vector<T> hw((size_t)(Kl > 0 ? Kl : 1), (T)1.0);
+            for (int i = 0; i < Kl; i++) hw[i] = (T)w[sx.perm[sx.o0 + i]];
+            int rc;
+            if (!d_wobs.p && (rc = d_wobs.alloc(hw.size()))) return rc;
+            HIPCHK(hipMemcpy(d_wobs.p, hw.data(), sizeof(T) * hw.size(), hipMemcpyHostToDevice));
+        }
+        return model_changed();
     }
 
     ba_red_jobs test_energy_jobs() const
@@ -1973,6 +2033,8 @@ int ba_solver_set_constant(ba_solver *s, const unsigned short *cam_mask, const u
 {
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_constant(cam_mask, pt_fixed);
 }
+int ba_solver_set_loss(ba_solver *s, int kind, double scale) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_loss(kind, scale); }
+int ba_solver_set_obs_weights(ba_solver *s, const double *w) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_obs_weights(w); }
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

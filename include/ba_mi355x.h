@@ -314,15 +314,20 @@ int ba_problem_gauge_mask(const ba_problem *p, int ref_cam, unsigned short *cam_
 
 /* ---- covariance blocks (no reference counterpart; Ceres' Covariance, g2o's computeMarginals) ---------------------------------------- */
 
-/* With J the Jacobian of the last ba_solver_linearize (robustified residuals, masked columns zero), F the set of free parameters and
- * H = (J'J + lambda I) restricted to F:   Sigma = H^-1 on F x F, exactly 0 in every row and column of a fixed parameter.
- * Sigma is the covariance of the estimate in the solver's own tangent parametrisation (camera block in the order of BA_GET_DX: T, omega,
- * f, k1, k2; point block x, y, z) for unit variance of the robustified residuals; scaling by a sigma^2 is the caller's.  lambda = 0 is
- * the meaningful value once the gauge is fixed (ba_problem_gauge_mask); lambda > 0 gives the damped inverse.
+/* With J the Jacobian of the last ba_solver_linearize (robustified, weighted residuals e of the measurement model in force, masked columns
+ * zero), F the set of free parameters and H = (J'J + lambda I) restricted to F:   Sigma = H^-1 on F x F, exactly 0 in every row and column
+ * of a fixed parameter.  Sigma is in the solver's own tangent parametrisation (camera block in the order of BA_GET_DX: T, omega, f, k1, k2;
+ * point block x, y, z).  With BA_LOSS_TRIVIAL and weights w_o = 1 / sigma_o (ba_solver_set_loss, ba_solver_set_obs_weights; sigma_o the
+ * standard deviation of observation o in pixels, per coordinate) J'J is the information matrix of the measurements and Sigma simply the
+ * covariance of the estimate -- nothing is left to scale.  Under a robust loss (the default psi included) Sigma is the Gauss-Newton
+ * covariance of the robustified problem: the inverse of J'J for e = sqrt(rho(s) / s) r, i.e. for unit variance of e, in which an
+ * observation beyond the loss's scale counts for little (psi: for nothing).  lambda = 0 is the meaningful value once the gauge is
+ * fixed (ba_problem_gauge_mask); lambda > 0 gives the damped inverse.  Any loss and any weights are accepted.
  * compute: assembles S(lambda) from the current linearisation as a trial does, factors the symmetrically scaled matrix
  * diag(S)^-1/2 S diag(S)^-1/2 (fixed rows: unit diagonal) by the dense LDL^T with the scaling stacked below it, and forms the inverse
  * of the free block on the device.  BA_CHOLESKY and BA_QRCHOL, BA_F64, shard_world == 1; anything else BA_ERR_ARG, as are lambda < 0 or
- * not finite, no ba_solver_linearize since creation / ba_solver_set_state / ba_minimize, and a mask set since the last linearisation.
+ * not finite, no ba_solver_linearize since creation / ba_solver_set_state / ba_minimize, and a mask or a measurement model set since the
+ * last linearisation.
  * BA_ERR_SINGULAR, no result left behind: a pivot <= 0 of S or of a free point's 3 x 3 block (lambda = 0 without a gauge mask, a
  * parameter nobody observes) -- found on the device, a flag word read back with the call.  x, xTest, the linearisation and the mask are
  * untouched: a ba_solver_try_step or ba_minimize behind it returns the bits it returns without it, and behind a ba_solver_try_step the
@@ -335,12 +340,38 @@ int ba_solver_covariance_compute(ba_solver *s, double lambda);
 /* Blocks of the last computed covariance.  cam_pairs: n_pairs x (a, b) -> 81 doubles each, row-major block Sigma_ab (Sigma_ba is its
  * transpose bit for bit); pt_ids: n_pts points in the PROBLEM's numbering -> 9 doubles each, computed on the device for these points
  * only (O(t^2) 9 x 9 blocks for a track of t observations).  Either list may be empty.  BA_ERR_ARG: no successful compute yet, or a
- * ba_solver_linearize / ba_solver_accept / ba_solver_set_state / ba_solver_set_constant / ba_minimize since (the result is stale), an
- * index out of range.  A ba_solver_try_step in between does not invalidate the result. */
+ * ba_solver_linearize / ba_solver_accept / ba_solver_set_state / ba_solver_set_constant / ba_solver_set_loss / ba_solver_set_obs_weights /
+ * ba_minimize since (the result is stale), an index out of range.  A ba_solver_try_step in between does not invalidate the result. */
 int ba_solver_covariance_get(ba_solver *s, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov);
 /* Device ms (HIP events): ms4 = {elimination + assembly of S + staging, factorisation, inverse from the factor} of the last compute and
  * the point kernel of the last ba_solver_covariance_get that asked for points. */
 int ba_solver_covariance_timing(ba_solver *s, double *ms4);
+
+/* ---- measurement model (no reference counterpart beyond its psi; Ceres' LossFunction, g2o's robust kernels and information) ---------- */
+
+/* With r_o = w_o (pi(cam, pt) - meas_o) the weighted reprojection residual of observation o in pixels (w_o = 1 without weights) and
+ * s = |r_o|^2, the solver minimises sum_o rho(s_o):
+ *   BA_LOSS_REFERENCE  psi(s) = s (2 - s / tau^2) / 4 below tau^2, tau^2 / 4 above (BAFunctor.h:147); scale = tau.  A new solver is
+ *                      (BA_LOSS_REFERENCE, 0.5): INLIER_THRESHOLD of bundle_adjustment_large.cpp:36, chosen for the BAL "-pre" files
+ *   BA_LOSS_TRIVIAL    s: plain least squares; scale is ignored
+ *   BA_LOSS_HUBER      s for s <= delta^2, 2 delta sqrt(s) - delta^2 above; scale = delta > 0
+ *   BA_LOSS_CAUCHY     c^2 log(1 + s / c^2); scale = c > 0
+ * the way the reference does for psi: the residual handed to LM is e_o = g r_o, g = sqrt(rho(s) / s), and J is the full derivative of e,
+ *   de/dr = g (I - rh rh') + (rho'(s) sqrt(s) / sqrt(rho(s))) rh rh',  rh = r / sqrt(s)
+ * (finite and continuous at s = 0, where g = sqrt(rho'(0)); BA_LOSS_TRIVIAL and Huber's quadratic part are e = r, de/dr = I exactly), so
+ * that sum e^2 = sum rho.  Every kind, both scalar types, sharded or not.  Everything built from e and J follows: S, rhs, lambda0, MOREQR's
+ * column norms, rho, the stop tests, the mask of ba_solver_set_constant (masked columns of the new J are zero), BA_ITERSCHUR's operator,
+ * the covariance.  BA_GET_RESIDUALS returns e.  ba_solver_stats keeps its meaning: the reference's statistics of the UNWEIGHTED pixel
+ * errors with the reference's threshold 0.5, whatever the model.
+ * w: K weights of the PROBLEM, in the order of the input file (NULL = none; a shard reads those of its own observations, and the solver
+ * applies its own observation order to them -- unsorted input included); copied.
+ * Either call takes effect at the next ba_solver_linearize or ba_minimize; a ba_solver_try_step before that returns BA_ERR_ARG, and a
+ * computed covariance becomes stale.  ba_solver_set_loss(BA_LOSS_REFERENCE, 0.5) together with ba_solver_set_obs_weights(NULL) restores
+ * the default path bit for bit.  BA_ERR_ARG, the solver unchanged: an unknown kind; a scale <= 0, NaN or infinite (in the solver's scalar
+ * type) for a kind that uses it; a weight that is not finite or <= 0. */
+typedef enum { BA_LOSS_REFERENCE = 0, BA_LOSS_TRIVIAL = 1, BA_LOSS_HUBER = 2, BA_LOSS_CAUCHY = 3 } ba_loss_kind;
+int ba_solver_set_loss(ba_solver *s, int kind, double scale);
+int ba_solver_set_obs_weights(ba_solver *s, const double *w /* K of the PROBLEM, file order; NULL = none */);
 
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);

@@ -39,6 +39,7 @@ EXPORTS = [
     "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes", "ba_solver_set_constant", "ba_problem_gauge_mask",
     "ba_solver_covariance_compute", "ba_solver_covariance_get", "ba_solver_covariance_timing",
     "ba_solver_set_loss", "ba_solver_set_obs_weights",
+    "ba_solver_set_point_priors", "ba_solver_set_centre_priors", "ba_solver_set_intrinsics_priors", "ba_solver_prior_energy",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -135,6 +136,10 @@ def lib():
         L.ba_solver_covariance_timing.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.ba_solver_set_obs_weights.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_set_point_priors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_solver_set_centre_priors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_solver_set_intrinsics_priors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_solver_prior_energy.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -361,6 +366,48 @@ class Solver:
             if w.shape != (self.problem.K,):
                 raise ValueError("w must have shape (%d,), got %s" % (self.problem.K, w.shape))
         _chk(lib().ba_solver_set_obs_weights(self._h, _p(w)), "ba_solver_set_obs_weights")
+
+    @staticmethod
+    def _prior_arrays(ids, x0, sqrt_info, sigma):
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        n = len(ids)
+        x0 = np.ascontiguousarray(np.asarray(x0, np.float64).reshape(n, 3))
+        if (sqrt_info is None) == (sigma is None):
+            raise ValueError("give sqrt_info or sigma, one of them")
+        if sqrt_info is None:
+            sg = np.broadcast_to(np.asarray(sigma, np.float64), (n, 3))
+            L = np.zeros((n, 3, 3))
+            for q in range(3):
+                L[:, q, q] = 1.0 / sg[:, q]
+        else:
+            L = np.asarray(sqrt_info, np.float64).reshape(n, 3, 3)
+        return n, ids, x0, np.ascontiguousarray(L)
+
+    def set_point_priors(self, ids, x0, sqrt_info=None, sigma=None):
+        """Gaussian priors e = L (X - x0) on the points `ids` of the problem from the next linearize() / minimize() on: sqrt_info (n, 3, 3)
+        is L, or sigma (a scalar or (n, 3)) gives L = diag(1 / sigma).  An empty list removes them (CHOLESKY, ITERSCHUR; one shard)."""
+        n, ids, x0, L = self._prior_arrays(ids, x0, sqrt_info, sigma)
+        _chk(lib().ba_solver_set_point_priors(self._h, n, _p(ids), _p(x0), _p(L)), "ba_solver_set_point_priors")
+
+    def set_centre_priors(self, ids, c0, sqrt_info=None, sigma=None):
+        """Gaussian priors e = L (C - c0) on the centres C = -R^T T of the cameras `ids` (e.g. GNSS positions); arguments as set_point_priors."""
+        n, ids, c0, L = self._prior_arrays(ids, c0, sqrt_info, sigma)
+        _chk(lib().ba_solver_set_centre_priors(self._h, n, _p(ids), _p(c0), _p(L)), "ba_solver_set_centre_priors")
+
+    def set_intrinsics_priors(self, ids, x0, sigma):
+        """Priors e_q = (x_q - x0_q) / sigma_q on (f, k1, k2) of the cameras `ids`, in the units of get(GET_CAMS)[:, 12:15]; sigma is a
+        scalar or (n, 3), and sigma_q = inf leaves parameter q without a row."""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        n = len(ids)
+        x0 = np.ascontiguousarray(np.asarray(x0, np.float64).reshape(n, 3))
+        w = np.ascontiguousarray(1.0 / np.broadcast_to(np.asarray(sigma, np.float64), (n, 3)))
+        _chk(lib().ba_solver_set_intrinsics_priors(self._h, n, _p(ids), _p(x0), _p(w)), "ba_solver_set_intrinsics_priors")
+
+    def prior_energy(self):
+        """Energies (sum of e^2) of the point, centre and intrinsics priors at x of the last linearize()."""
+        out = np.empty(3)
+        _chk(lib().ba_solver_prior_energy(self._h, _p(out)), "ba_solver_prior_energy")
+        return out
 
     def pcg_stats(self, reset=False):
         """ITERSCHUR: solves and iterations counted on the device; the last solve's iterations, convergence and |rhs - S dx_c| / |rhs|."""

@@ -220,6 +220,26 @@ __device__ __forceinline__ void ba_cov_point_u(int o0, int o1, int K, const T *_
     U[0] += lambda; U[3] += lambda; U[5] += lambda;
 }
 
+// U0 = the linearisation's own [6][Ml] blocks (k_point_prep + the point priors, ba_prior.hip.h) instead of the sum over Jp: a solver with
+// priors has rows of J that are in no observation
+template <typename T> __device__ __forceinline__ void ba_cov_point_u0(int j, int Ml, const T *__restrict__ U0, T lambda, T (&U)[6])
+{
+#pragma unroll
+    for (int q = 0; q < 6; q++) U[q] = U0[(size_t)q * Ml + j];
+    U[0] += lambda; U[3] += lambda; U[5] += lambda;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_cov_points_check_u0(int Ml, const T *__restrict__ U0, const unsigned char *__restrict__ pfix,
+                                                             const T *__restrict__ lam, int *__restrict__ flag)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= Ml || (pfix && pfix[j])) return;
+    T U[6];
+    ba_cov_point_u0<T>(j, Ml, U0, *lam, U);
+    ba_cov_u3<T> f;
+    if (!ba_cov_ldl3<T>(U, f)) *flag = 1;
+}
+
 // every free point: U_p positive definite, or the flag word (one thread per point)
 template <typename T>
 __global__ __launch_bounds__(256) void k_cov_points_check(int Ml, int K, const int *__restrict__ pt_ptr, const T *__restrict__ Jp,
@@ -235,11 +255,12 @@ __global__ __launch_bounds__(256) void k_cov_points_check(int Ml, int K, const i
 
 // One wavefront per point asked for: M = sum over the pairs (o, o') of its track of G_o^T Sigma_{c(o) c(o')} G_o' (the lanes stride
 // over the pairs, a fixed-order wave sum closes it), then Sigma_pp = U^-1 + U^-1 M U^-1, symmetrised.  A fixed point: zeros.
-template <typename T, bool AOS>
-__global__ __launch_bounds__(64) void k_cov_points(int n_pts, const int *__restrict__ ids, int K, const int *__restrict__ pt_ptr,
+// (FROMU0: U of the point from the linearisation's blocks, k_cov_points_u0 below)
+template <typename T, bool AOS, bool FROMU0>
+__device__ __forceinline__ void ba_cov_points_body(int n_pts, const int *__restrict__ ids, int K, const int *__restrict__ pt_ptr,
                                                    const int *__restrict__ obs_cam, const T *__restrict__ Jc, const T *__restrict__ Jp,
                                                    const unsigned char *__restrict__ pfix, T lambda, int ldc, const T *__restrict__ C,
-                                                   double *__restrict__ out)
+                                                   double *__restrict__ out, const T *__restrict__ U0, int Ml)
 {
     const int j = ids[blockIdx.x], lane = threadIdx.x;
     double *o9 = out + (size_t)9 * blockIdx.x;
@@ -249,7 +270,8 @@ __global__ __launch_bounds__(64) void k_cov_points(int n_pts, const int *__restr
     }
     const int o0 = pt_ptr[j], o1 = pt_ptr[j + 1], t = o1 - o0;
     T U[6];
-    ba_cov_point_u<T>(o0, o1, K, Jp, lambda, lane, 64, U);
+    if constexpr (FROMU0) ba_cov_point_u0<T>(j, Ml, U0, lambda, U);
+    else ba_cov_point_u<T>(o0, o1, K, Jp, lambda, lane, 64, U);
     T m[3][3];
 #pragma unroll
     for (int x = 0; x < 3; x++)
@@ -324,6 +346,22 @@ __global__ __launch_bounds__(64) void k_cov_points(int n_pts, const int *__restr
     for (int x = 0; x < 3; x++)
 #pragma unroll
         for (int y = 0; y < 3; y++) o9[3 * x + y] = (double)((T)0.5 * (R[x][y] + R[y][x]));
+}
+template <typename T, bool AOS>
+__global__ __launch_bounds__(64) void k_cov_points(int n_pts, const int *__restrict__ ids, int K, const int *__restrict__ pt_ptr,
+                                                   const int *__restrict__ obs_cam, const T *__restrict__ Jc, const T *__restrict__ Jp,
+                                                   const unsigned char *__restrict__ pfix, T lambda, int ldc, const T *__restrict__ C,
+                                                   double *__restrict__ out)
+{
+    ba_cov_points_body<T, AOS, false>(n_pts, ids, K, pt_ptr, obs_cam, Jc, Jp, pfix, lambda, ldc, C, out, (const T *)nullptr, 0);
+}
+template <typename T, bool AOS>
+__global__ __launch_bounds__(64) void k_cov_points_u0(int n_pts, const int *__restrict__ ids, int K, const int *__restrict__ pt_ptr,
+                                                      const int *__restrict__ obs_cam, const T *__restrict__ Jc, const T *__restrict__ Jp,
+                                                      const unsigned char *__restrict__ pfix, T lambda, int ldc, const T *__restrict__ C,
+                                                      double *__restrict__ out, const T *__restrict__ U0, int Ml)
+{
+    ba_cov_points_body<T, AOS, true>(n_pts, ids, K, pt_ptr, obs_cam, Jc, Jp, pfix, lambda, ldc, C, out, U0, Ml);
 }
 
 #endif

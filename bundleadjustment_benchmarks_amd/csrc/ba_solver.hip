@@ -12,6 +12,7 @@
 #include "ba_qr.hip.h"
 #include "ba_pcg.hip.h"
 #include "ba_cov.hip.h"
+#include "ba_prior.hip.h"
 
 #include <chrono>
 #include <cmath>
@@ -96,6 +97,8 @@ struct SolverBase {
     virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
     virtual int set_loss(int kind, double scale) = 0;
     virtual int set_obs_weights(const double *w) = 0;
+    virtual int set_priors(int type, int n, const int *ids, const double *x0, const double *info) = 0;
+    virtual int prior_energy(double *out3) = 0;
     virtual size_t device_bytes() const = 0;
     virtual int cov_compute(double lambda) = 0;
     virtual int cov_get(int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov) = 0;
@@ -624,13 +627,15 @@ template <typename T> struct Solver final : SolverBase {
         // energy sum rides on the last launch of launch_grad (no k_reduce_scalars launch) unless MOREQR's outer QR follows it
         ba_red_jobs jobs{};
         int nj = 0;
-        jobs.j[nj++] = {d_part_e.p, gE, 0, sharded() ? SC_ELOC : SC_ENERGY};
-        const bool tail = go != nullptr && !want_dmax && kind != BA_MOREQR;
+        jobs.j[nj++] = {d_part_e.p, gE + 3 * gP, 0, sharded() ? SC_ELOC : SC_ENERGY}; // (gP = 0 without priors)
+        const bool tail = go != nullptr && !want_dmax && kind != BA_MOREQR && !priors(); // (priors: their energy partials come behind launch_grad)
         // behind a trial the point part of J^T r / J^T J and (CHOLESKY) the elimination of the next trial are part of the k_eval launch;
         // the first, host-synchronous linearisation (lambda0 is not known yet, max diag J^T J is wanted) keeps the separate launches
+        // priors: the prior kernel behind the linearisation's launches, in front of the trial's k_elim_chol (fused_records())
         const bool fz = fuse && go != nullptr && !want_dmax;
         launch_eval(true, go ? 1 : 0, go, go != nullptr, fz);
         launch_grad(go, tail ? &jobs.j[0] : nullptr, !fz);
+        if (priors()) launch_prior(true, go ? 1 : 0, go);
         if (kind == BA_MOREQR) { // m_solver.compute(J) + Q^T r, once per outer iteration (BacktrackLevMarqMore.h:288-291): the point blocks ...
             launch_elim_qr(d_scal.p + SC_ZERO, d_rec0.p, d_dinv0.p, d_tvec0.p, d_tri0.p, go, /*thin Q for J2bot*/ more_qr());
             if (more_qr() && (rc = launch_more_outer(go))) return rc; // ... and the dense QR of J2bot(lambda = 0); its part 2 follows where a collective may stand
@@ -641,7 +646,7 @@ template <typename T> struct Solver final : SolverBase {
             T *tmp = d_dxc.p;
             hipLaunchKernelGGL((k_vdiag<T>), dim3((D + 255) / 256), dim3(256), 0, st, N, d_V.p, tmp);
             if ((rc = allreduce(tmp, (size_t)D, 0))) return rc;
-            jobs.j[nj++] = {d_part_pm.p, gM, 1, SC_DMAX_P};
+            jobs.j[nj++] = {d_part_pm.p, gM + gP, 1, SC_DMAX_P}; // (behind the points' own: the diagonals a point prior has raised)
             jobs.j[nj++] = {tmp, D, 1, SC_DMAX_C};
         }
         hipLaunchKernelGGL((k_reduce_scalars<T>), dim3(nj), dim3(256), 0, st, jobs, d_scal.p, go, &d_lm.p->t_end);
@@ -655,7 +660,7 @@ template <typename T> struct Solver final : SolverBase {
         if (chol_elim()) {
             hipLaunchKernelGGL((k_elim_chol<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
                                d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
-                               fuse ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
+                               fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
         } else if (kind == BA_MOREQR) {
             if (Kl > 0) // BacktrackLevMarqMore.h:297-345, the per-trial QR of [R ; sqrt(lambda) I]
                 hipLaunchKernelGGL((k_more_trial<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_scal.p + SC_LAMBDA,
@@ -990,7 +995,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs);
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs) + prior_bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1045,6 +1050,10 @@ template <typename T> struct Solver final : SolverBase {
             HIPCHK(hipMemsetAsync(d_cov.p, 0, sizeof(T) * cov_nmat(), st));
             hipLaunchKernelGGL((k_cov_scale<T>), dim3((D + 255) / 256), dim3(256), 0, st, D, ld, (const T *)d_S.p, (const unsigned short *)d_cmask.p,
                                cov_sc(), d_cov_flag.p);
+            if (priors()) // (a point prior is in U0 and in no observation's Jp)
+                hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)d_pfix.p,
+                                   (const T *)(d_scal.p + SC_LAMBDA), d_cov_flag.p);
+            else
             hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
                                (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), d_cov_flag.p);
             hipLaunchKernelGGL((k_cov_stage<T>), dim3(((D + NB - 1) / NB) * NB), dim3(256), 0, st, D, Dp, ld, (const T *)d_S.p, (const T *)cov_sc(), ldc, d_cov.p);
@@ -1099,7 +1108,11 @@ template <typename T> struct Solver final : SolverBase {
                 HIPCHK(hipMemcpy(d_idx.p, pt_ids, sizeof(int) * (size_t)n_pts, hipMemcpyHostToDevice));
                 // J of the linearisation, not the elimination's records: those are a later trial's by now
                 HIPCHK(hipEventRecord(ev[EV_T4], st));
-                if (chol_elim())
+                if (priors()) // (CHOLESKY: the only kind with both)
+                    hipLaunchKernelGGL((k_cov_points_u0<T, true>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
+                                       (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
+                                       (const T *)d_cov.p, d_out.p, (const T *)d_U0.p, Ml);
+                else if (chol_elim())
                     hipLaunchKernelGGL((k_cov_points<T, true>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
                                        (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
                                        (const T *)d_cov.p, d_out.p);
@@ -1244,10 +1257,116 @@ template <typename T> struct Solver final : SolverBase {
         return model_changed();
     }
 
+    // ---- Gaussian priors (ba_solver_set_point_priors / _centre_priors / _intrinsics_priors; ba_prior.hip.h) ------
+    // Compact device lists per type; the block partials of k_prior live behind k_eval's in d_part_e (energies, 3 gP) and behind
+    // k_point_prep's in d_part_pm (point diagonals, gP), so that the existing second-stage jobs sum them in their fixed order.  No prior:
+    // no list, gP = 0, the buffers at their old sizes and not one launch or argument more.
+    DevBuf<int> d_pr_id[3], d_pr_lonely; // d_pr_lonely: the points with a prior and no observation (k_prior_lonely)
+    DevBuf<T> d_pr_x0[3], d_pr_info[3], d_part_pr; // d_part_pr: [3][gP] prior energies of the last linearisation
+    int n_pr[3] = {0, 0, 0};
+    int gP = 0;
+    bool priors() const { return gP > 0; }
+    // The fused linearisation eliminates the next trial's points from registers, before a prior could join U0: with priors its records
+    // are not used -- every trial runs k_elim_chol on the U0 / gp that k_prior has completed -- while J, U0, gp and the energy partials
+    // still come from the kernel a solver without priors runs (so priors without information leave its bits alone, fp32 included,
+    // where the separate-launch linearisation does not reproduce the fused one's bits).
+    bool fused_records() const { return fuse && !priors(); }
+    size_t prior_bytes() const
+    {
+        size_t n = bytes_of(d_part_pr) + bytes_of(d_pr_lonely);
+        for (int q = 0; q < 3; q++) n += bytes_of(d_pr_id[q]) + bytes_of(d_pr_x0[q]) + bytes_of(d_pr_info[q]);
+        return n;
+    }
+    // lin: the linearisation part (adds into U0 / gp / V / gc of the state `which`); else the energy at xTest alone
+    void launch_prior(bool lin, int which, const int *go)
+    {
+        ba_prior_args<T> pa{n_pr[0], n_pr[1], n_pr[2], d_pr_id[0].p, d_pr_id[1].p, d_pr_id[2].p, d_pr_x0[0].p, d_pr_info[0].p,
+                            d_pr_x0[1].p, d_pr_info[1].p, d_pr_x0[2].p, d_pr_info[2].p};
+#define BA_PRIOR(L, M) hipLaunchKernelGGL((k_prior<T, L, M>), dim3(gP), dim3(256), 0, st, pa, N, Ml, (const T *)d_cam[which].p, (const T *)d_pts[which].p, \
+                                          d_U0.p, d_gp.p, d_V.p, d_gc.p, d_part_e.p + gE, d_part_pr.p, d_part_pm.p + gM, go,                         \
+                                          (const unsigned short *)d_cmask.p, (const unsigned char *)d_pfix.p)
+        if (!lin) BA_PRIOR(false, false);
+        else if (masked) BA_PRIOR(true, true);
+        else BA_PRIOR(true, false);
+#undef BA_PRIOR
+    }
+    // type 0 points (info = L, 9 per prior), 1 centres (L), 2 intrinsics (info = w, 3 per prior)
+    int set_priors(int type, int n, const int *ids, const double *x0, const double *info) override
+    {
+        if (!chol_elim() || sharded() || n < 0 || (n > 0 && (!ids || !x0 || !info))) return BA_ERR_ARG;
+        const int lim = type == 0 ? sx.M : N, ni = type == 2 ? 3 : 9;
+        if (n > lim) return BA_ERR_ARG; // (some index is listed twice)
+        {
+            std::vector<char> seen((size_t)(lim > 0 ? lim : 1), 0);
+            for (int q = 0; q < n; q++) {
+                if (ids[q] < 0 || ids[q] >= lim || seen[ids[q]]) return BA_ERR_ARG;
+                seen[ids[q]] = 1;
+            }
+        }
+        for (size_t q = 0; q < (size_t)3 * n; q++)
+            if (!std::isfinite(x0[q]) || !std::isfinite((T)x0[q])) return BA_ERR_ARG;
+        for (size_t q = 0; q < (size_t)ni * n; q++)
+            if (!std::isfinite(info[q]) || !std::isfinite((T)info[q])) return BA_ERR_ARG;
+        HIPCHK(hipStreamSynchronize(st));
+        int cnt[3] = {n_pr[0], n_pr[1], n_pr[2]};
+        cnt[type] = n;
+        const int tot = cnt[0] + cnt[1] + cnt[2], gp_new = (tot + 255) / 256;
+        int rc;
+        // everything that can fail first: the solver is unchanged behind an error
+        DevBuf<int> nid, nlone;
+        DevBuf<T> nx0, ninfo, npe, npm, npr;
+        if (type == 0) {
+            std::vector<int> lone;
+            for (int q = 0; q < n; q++)
+                if (sx.pt_ptr[ids[q] + 1] == sx.pt_ptr[ids[q]]) lone.push_back(ids[q]);
+            if ((rc = nlone.upload(lone))) { (void)hipGetLastError(); return rc; }
+        }
+        if (n > 0) {
+            std::vector<int> hid(ids, ids + n);
+            std::vector<T> hx((size_t)3 * n), hi((size_t)ni * n);
+            for (size_t q = 0; q < hx.size(); q++) hx[q] = (T)x0[q];
+            for (size_t q = 0; q < hi.size(); q++) hi[q] = (T)info[q];
+            if ((rc = nid.upload(hid)) || (rc = nx0.upload(hx)) || (rc = ninfo.upload(hi))) { (void)hipGetLastError(); return rc; }
+        }
+        if (gp_new != gP) {
+            if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gp_new)) || (rc = npm.alloc((size_t)gM + gp_new)) ||
+                (rc = npr.alloc(3 * (size_t)gp_new))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
+            HIPCHK(hipMemset(npm.p, 0, sizeof(T) * npm.n));
+            if (npr.p) HIPCHK(hipMemset(npr.p, 0, sizeof(T) * npr.n));
+            std::swap(d_part_e.p, npe.p); std::swap(d_part_e.n, npe.n);
+            std::swap(d_part_pm.p, npm.p); std::swap(d_part_pm.n, npm.n);
+            std::swap(d_part_pr.p, npr.p); std::swap(d_part_pr.n, npr.n);
+            gP = gp_new;
+        }
+        std::swap(d_pr_id[type].p, nid.p); std::swap(d_pr_id[type].n, nid.n);
+        std::swap(d_pr_x0[type].p, nx0.p); std::swap(d_pr_x0[type].n, nx0.n);
+        std::swap(d_pr_info[type].p, ninfo.p); std::swap(d_pr_info[type].n, ninfo.n);
+        if (type == 0) { std::swap(d_pr_lonely.p, nlone.p); std::swap(d_pr_lonely.n, nlone.n); }
+        n_pr[type] = n;
+        return model_changed(); // (the old buffers leave with the locals)
+    }
+    // the three sums of the last linearisation's partials, in index order
+    int prior_energy(double *out3) override
+    {
+        if (!chol_elim() || sharded() || !have_lin || mask_pending) return BA_ERR_ARG;
+        out3[0] = out3[1] = out3[2] = 0.0;
+        if (!priors()) return BA_OK;
+        std::vector<T> h;
+        int rc;
+        if ((rc = dl(d_part_pr.p, 3 * (size_t)gP, h))) return rc;
+        for (int q = 0; q < 3; q++) {
+            T a = 0;
+            for (int b = 0; b < gP; b++) a += h[(size_t)q * gP + b];
+            out3[q] = (double)a;
+        }
+        return BA_OK;
+    }
+
     ba_red_jobs test_energy_jobs() const
     {
         ba_red_jobs jobs{};
-        jobs.j[0] = {d_part_e.p, gE, 0, SC_ETEST};
+        jobs.j[0] = {d_part_e.p, gE + 3 * gP, 0, SC_ETEST}; // (gP = 0 without priors)
         jobs.j[1] = {d_part_bs.p, gB, 0, SC_RHO_P};
         jobs.j[2] = {d_part_bs.p + gB, gB, 0, SC_DN_P};
         return jobs;
@@ -1256,6 +1375,7 @@ template <typename T> struct Solver final : SolverBase {
     void launch_test_energy(bool reduce = true)
     {
         launch_eval(false, 1);
+        if (priors()) launch_prior(false, 1, nullptr);
         if (reduce) hipLaunchKernelGGL((k_reduce_scalars<T>), dim3(3), dim3(256), 0, st, test_energy_jobs(), d_scal.p, (const int *)nullptr);
     }
 
@@ -1313,6 +1433,16 @@ template <typename T> struct Solver final : SolverBase {
         }
         if ((rc = mark(EV_T4))) return rc;
         launch_backsub_retract();
+        if (d_pr_lonely.n > 0) { // (points with a prior and no observation: none on a usual problem, no launch then)
+            if (masked)
+                hipLaunchKernelGGL((k_prior_lonely<T, true>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
+                                   (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p, d_part_bs.p, gB,
+                                   (const unsigned char *)d_pfix.p);
+            else
+                hipLaunchKernelGGL((k_prior_lonely<T, false>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
+                                   (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p, d_part_bs.p, gB,
+                                   (const unsigned char *)nullptr);
+        }
         if ((rc = mark(EV_T5))) return rc;
         launch_test_energy(step_level || !ctl_reduces()); // (single shard: k_lm_control sums the three partial arrays at its head)
         return BA_OK;
@@ -1850,7 +1980,7 @@ template <typename T> struct Solver final : SolverBase {
         for (int k = 0; k < reps; k++) {
             switch (phase) {
             case 0: launch_eval(false, 0); break;
-            case 1: launch_eval(true, 0); launch_grad(); break;
+            case 1: launch_eval(true, 0); launch_grad(); if (priors()) launch_prior(true, 0, nullptr); break;
             case 2: launch_eliminate(); break;
             case 3: launch_assemble(); break; // (QRKIT: J2bot instead of S)
             case 4:
@@ -1863,6 +1993,7 @@ template <typename T> struct Solver final : SolverBase {
             case 8: // the linearisation as ba_minimize runs it behind an accepted step: fused point part (+ CHOLESKY: the next trial's records)
                 launch_eval(true, 0, nullptr, false, true);
                 launch_grad(nullptr, nullptr, !fuse);
+                if (priors()) launch_prior(true, 0, nullptr);
                 break;
             case 6: // dense factorisation only (k_ldlt_panel + k_ldlt_step / k_ldlt_update; QRKIT: the Householder QR + solve): events around it, per rep
             case 7: // backward sweep only (k_ldlt_backflow; QRKIT: nothing, the solve is part of 6)
@@ -2035,6 +2166,19 @@ int ba_solver_set_constant(ba_solver *s, const unsigned short *cam_mask, const u
 }
 int ba_solver_set_loss(ba_solver *s, int kind, double scale) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_loss(kind, scale); }
 int ba_solver_set_obs_weights(ba_solver *s, const double *w) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_obs_weights(w); }
+int ba_solver_set_point_priors(ba_solver *s, int n, const int *pt_ids, const double *x0, const double *sqrt_info)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_priors(0, n, pt_ids, x0, sqrt_info);
+}
+int ba_solver_set_centre_priors(ba_solver *s, int n, const int *cam_ids, const double *c0, const double *sqrt_info)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_priors(1, n, cam_ids, c0, sqrt_info);
+}
+int ba_solver_set_intrinsics_priors(ba_solver *s, int n, const int *cam_ids, const double *x0, const double *w)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_priors(2, n, cam_ids, x0, w);
+}
+int ba_solver_prior_energy(ba_solver *s, double *out3) { return !(s && out3) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->prior_energy(out3); }
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

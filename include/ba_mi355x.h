@@ -373,6 +373,38 @@ typedef enum { BA_LOSS_REFERENCE = 0, BA_LOSS_TRIVIAL = 1, BA_LOSS_HUBER = 2, BA
 int ba_solver_set_loss(ba_solver *s, int kind, double scale);
 int ba_solver_set_obs_weights(ba_solver *s, const double *w /* K of the PROBLEM, file order; NULL = none */);
 
+/* ---- Gaussian priors (no reference counterpart; Ceres' residual blocks on one parameter block, g2o's unary edges) --------------------- */
+
+/* Soft constraints on the parameters themselves: the solver minimises  sum_o rho(|r_o|^2) + sum_priors |e|^2  -- priors carry no robust
+ * loss -- with, in the units of BA_GET_CAMS / BA_GET_POINTS (the solver's own parametrisation: f, k1, k2 as the solver holds them after
+ * the load-time scaling, f = -f_file, k1 = k1_file f^2, k2 = k2_file f^4),
+ *   point       e = L (X_p - X0)                              3 rows, Jacobian L on the point's columns
+ *   centre      e = L (C_a - C0),  C_a = -R_a^T T_a           3 rows, Jacobian L [-R^T | -R^T [T]x | 0 0 0] on the camera's columns
+ *                                                             (T, omega, f, k1, k2), for the retraction T + dT, R <- Rodrigues(d omega) R
+ *   intrinsics  e_q = w_q (x_q - x0_q),  q in (f, k1, k2)     up to 3 rows, Jacobian w_q on column 6 + q; w_q = 0: no row for q
+ * L: any real 3 x 3, row-major (usually the upper Cholesky factor of the inverse covariance; diag(1 / sigma) for independent axes).
+ * Prior rows are rows of J like any other: they enter J'J (U of the point, the camera's 9 x 9 block), g = -J'e (BA_GET_GRAD), the
+ * energy that ba_solver_linearize, ba_solver_try_step and the LM table report, lambda0 = 1e-12 max diag J'J, rho and the stop tests, S,
+ * rhs, BA_ITERSCHUR's operator and preconditioner, and the covariance (ba_solver_covariance_compute(s, 0) of a problem whose gauge the
+ * priors fix is BA_OK).  BA_GET_RESIDUALS / BA_GET_JC / BA_GET_JP stay the 2K observation rows, ba_solver_stats keeps its meaning.
+ * With ba_solver_set_constant the prior's columns of a fixed parameter are zero like every other column of J; a prior whose parameters
+ * are all fixed is a constant in the energy.
+ * ids: n indices of the PROBLEM, each at most once; x0 / c0: 3n; sqrt_info: 9n; w: 3n; copied.  n = 0 removes the priors of that type;
+ * with all three removed the solver runs the path without priors again, bit for bit.  A call takes effect at the next
+ * ba_solver_linearize or ba_minimize; a ba_solver_try_step before that returns BA_ERR_ARG, and a computed covariance becomes stale.
+ * BA_CHOLESKY and BA_ITERSCHUR (they share the point elimination, for which a prior is an addition to blocks that already exist),
+ * BA_F64 and BA_F32, shard_world == 1.  With priors set every trial runs the point elimination as a launch of its own (the fused
+ * linearisation eliminates the next trial's points before a prior could join them: those records are not used).
+ * BA_ERR_ARG, the solver unchanged: another kind (the QR kinds would need extra rows in the per-point QR and in J2bot: not built), a
+ * sharded solver (not built), an index out of range or listed twice, a value that is not finite (in the solver's scalar type), n < 0,
+ * a NULL array with n > 0. */
+int ba_solver_set_point_priors(ba_solver *s, int n, const int *pt_ids, const double *x0, const double *sqrt_info);
+int ba_solver_set_centre_priors(ba_solver *s, int n, const int *cam_ids, const double *c0, const double *sqrt_info);
+int ba_solver_set_intrinsics_priors(ba_solver *s, int n, const int *cam_ids, const double *x0, const double *w);
+/* out3 = energy of the point, centre and intrinsics priors at x of the last linearisation (sum of e^2, each group; zeros without
+ * priors).  BA_ERR_ARG: another kind, sharded, no linearisation, or a model set since the last one. */
+int ba_solver_prior_energy(ba_solver *s, double *out3);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);

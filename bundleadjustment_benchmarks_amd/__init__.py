@@ -40,6 +40,7 @@ EXPORTS = [
     "ba_solver_covariance_compute", "ba_solver_covariance_get", "ba_solver_covariance_timing",
     "ba_solver_set_loss", "ba_solver_set_obs_weights",
     "ba_solver_set_point_priors", "ba_solver_set_centre_priors", "ba_solver_set_intrinsics_priors", "ba_solver_prior_energy",
+    "ba_solver_set_relative_poses", "ba_solver_relative_pose_energy",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -140,6 +141,8 @@ def lib():
         L.ba_solver_set_centre_priors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_solver_set_intrinsics_priors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_solver_prior_energy.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_set_relative_poses.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.ba_solver_relative_pose_energy.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -409,6 +412,36 @@ class Solver:
         _chk(lib().ba_solver_prior_energy(self._h, _p(out)), "ba_solver_prior_energy")
         return out
 
+    def set_relative_poses(self, pairs, R0, t0, sqrt_info_rot=None, sqrt_info_trans=None, sigma_rot=None, sigma_trans=None):
+        """Relative-pose constraints e_t = L_t (t_ab - t0), e_r = L_r Log(R_ab R0^T) between the camera pairs (a, b) of `pairs` (n, 2), with
+        R_ab = R_b R_a^T, t_ab = T_b - R_ab T_a, from the next linearize() / minimize() on.  R0 (n, 3, 3), t0 (n, 3); per kind either
+        sqrt_info_* (n, 3, 3) = L or sigma_* (a scalar or (n, 3): L = diag(1 / sigma), radians / the units of T); neither: no rows of that
+        kind.  An empty list removes the constraints (CHOLESKY, ITERSCHUR; one shard)."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        n = len(pairs)
+        R0 = np.ascontiguousarray(np.asarray(R0, np.float64).reshape(n, 3, 3))
+        t0 = np.ascontiguousarray(np.asarray(t0, np.float64).reshape(n, 3))
+
+        def info(L, sigma, what):
+            if L is not None and sigma is not None:
+                raise ValueError("give sqrt_info_%s or sigma_%s, not both" % (what, what))
+            out = np.zeros((n, 3, 3))
+            if L is not None:
+                out[:] = np.asarray(L, np.float64).reshape(n, 3, 3)
+            elif sigma is not None:
+                sg = np.broadcast_to(np.asarray(sigma, np.float64), (n, 3))
+                for q in range(3):
+                    out[:, q, q] = 1.0 / sg[:, q]
+            return np.ascontiguousarray(out)
+        Lr, Lt = info(sqrt_info_rot, sigma_rot, "rot"), info(sqrt_info_trans, sigma_trans, "trans")
+        _chk(lib().ba_solver_set_relative_poses(self._h, n, _p(pairs), _p(R0), _p(t0), _p(Lr), _p(Lt)), "ba_solver_set_relative_poses")
+
+    def relative_pose_energy(self):
+        """(sum |e_r|^2, sum |e_t|^2) of the relative-pose constraints at x of the last linearize()."""
+        out = np.empty(2)
+        _chk(lib().ba_solver_relative_pose_energy(self._h, _p(out)), "ba_solver_relative_pose_energy")
+        return out
+
     def pcg_stats(self, reset=False):
         """ITERSCHUR: solves and iterations counted on the device; the last solve's iterations, convergence and |rhs - S dx_c| / |rhs|."""
         st = PCGStats()
@@ -474,6 +507,15 @@ class Solver:
 
 
 COMM_ID_BYTES = 128
+
+
+def relative_pose(cam15, a, b):
+    """(R_ab, t_ab) = (R_b R_a^T, T_b - R_ab T_a) of cameras a and b of a state as Solver.get(GET_CAMS) returns it (host only): the
+    pose of a's frame seen from b's, x_b = R_ab x_a + t_ab -- what Solver.set_relative_poses constrains."""
+    c = np.asarray(cam15, np.float64).reshape(-1, 15)
+    Ra, Rb = c[a, :9].reshape(3, 3), c[b, :9].reshape(3, 3)
+    Rab = Rb @ Ra.T
+    return Rab, c[b, 9:12] - Rab @ c[a, 9:12]
 
 
 def comm_unique_id():

@@ -25,6 +25,7 @@
 #define BA_PCG_HIP_H
 
 #include "ba_kernels.hip.h"
+#include "ba_relpose.hip.h"
 
 #define BA_PCG_CW 9 /* scalars per camera chunk of the camera pass in the chunk slab */
 
@@ -368,6 +369,38 @@ __global__ __launch_bounds__(256) void k_pcg_cam(int k, int N, const int *__rest
     }
     acc = block_reduce<double, false>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// Relative-pose constraints (ba_relpose.hip.h), directly behind k_pcg_cam and with its thread layout: y_a,r += sum over the camera's
+// incident constraints (H_ab v_b)_r in the CSR's order, and the block partial follows -- v'y gains the block's sum of v_r times that
+// term, |rhs - y|^2 (FINAL) is formed again from the new y in k_pcg_cam's order.  A launch of its own and not an instantiation of
+// k_pcg_cam: which products of a sum the compiler fuses is its choice per instantiation (in fp32 k_pcg_cam's V_a v is unfused, the same
+// lines with the constraint term behind them came out fused), and constraints without information must leave every bit of the solve alone
+// -- here they add exact zeros to y and to the partial.
+template <typename T, bool FINAL>
+__global__ __launch_bounds__(256) void k_pcg_relpose(int k, int N, ba_relpose_csr<T> cs, const T *__restrict__ z, const T *__restrict__ p,
+                                                     const T *__restrict__ x, const T *__restrict__ rhs, const double *__restrict__ part_rz,
+                                                     int gc, T *__restrict__ y, double *__restrict__ part, const ba_pcg_dev *__restrict__ pcg)
+{
+    __shared__ double red[4];
+    T beta = 0;
+    if (!FINAL) {
+        if (pcg->done) return;
+        beta = (T)ba_pcg_beta(k, part_rz, gc, red);
+    }
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t a = idx / 9;
+    const int r = (int)(idx - 9 * a);
+    double acc = 0;
+    if (a < (size_t)N) {
+        const T rp = ba_relpose_matvec_row<T>(cs, (int)a, r, [&](size_t o) { return FINAL ? x[o] : z[o] + beta * p[o]; });
+        const T yr = y[9 * a + r] + rp;
+        y[9 * a + r] = yr;
+        if (FINAL) { const double d = (double)rhs[9 * a + r] - (double)yr; acc = d * d; }
+        else acc = (double)(z[9 * a + r] + beta * p[9 * a + r]) * (double)rp;
+    }
+    acc = block_reduce<double, false>(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = FINAL ? acc : part[blockIdx.x] + acc;
 }
 
 // Per camera (one thread): alpha_k = r_k'z_k / p_k'S p_k; x += alpha p_k; r -= alpha S p_k; p <- p_k; z = M^-1 r; the block partials of

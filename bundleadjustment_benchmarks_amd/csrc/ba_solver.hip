@@ -13,7 +13,9 @@
 #include "ba_pcg.hip.h"
 #include "ba_cov.hip.h"
 #include "ba_prior.hip.h"
+#include "ba_relpose.hip.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -99,6 +101,8 @@ struct SolverBase {
     virtual int set_obs_weights(const double *w) = 0;
     virtual int set_priors(int type, int n, const int *ids, const double *x0, const double *info) = 0;
     virtual int prior_energy(double *out3) = 0;
+    virtual int set_relposes(int n, const int *pairs, const double *R0, const double *t0, const double *Lr, const double *Lt) = 0;
+    virtual int relpose_energy(double *out2) = 0;
     virtual size_t device_bytes() const = 0;
     virtual int cov_compute(double lambda) = 0;
     virtual int cov_get(int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov) = 0;
@@ -627,8 +631,8 @@ template <typename T> struct Solver final : SolverBase {
         // energy sum rides on the last launch of launch_grad (no k_reduce_scalars launch) unless MOREQR's outer QR follows it
         ba_red_jobs jobs{};
         int nj = 0;
-        jobs.j[nj++] = {d_part_e.p, gE + 3 * gP, 0, sharded() ? SC_ELOC : SC_ENERGY}; // (gP = 0 without priors)
-        const bool tail = go != nullptr && !want_dmax && kind != BA_MOREQR && !priors(); // (priors: their energy partials come behind launch_grad)
+        jobs.j[nj++] = {d_part_e.p, gE + 3 * gP + 2 * gR, 0, sharded() ? SC_ELOC : SC_ENERGY}; // (gP = 0 without priors, gR = 0 without constraints)
+        const bool tail = go != nullptr && !want_dmax && kind != BA_MOREQR && !priors() && !relposes(); // (their energy partials come behind launch_grad)
         // behind a trial the point part of J^T r / J^T J and (CHOLESKY) the elimination of the next trial are part of the k_eval launch;
         // the first, host-synchronous linearisation (lambda0 is not known yet, max diag J^T J is wanted) keeps the separate launches
         // priors: the prior kernel behind the linearisation's launches, in front of the trial's k_elim_chol (fused_records())
@@ -636,6 +640,9 @@ template <typename T> struct Solver final : SolverBase {
         launch_eval(true, go ? 1 : 0, go, go != nullptr, fz);
         launch_grad(go, tail ? &jobs.j[0] : nullptr, !fz);
         if (priors()) launch_prior(true, go ? 1 : 0, go);
+        // relative-pose constraints: records, then the per-camera gather into V / gc.  They touch no point block, so the fused pass's
+        // elimination records stay valid (fused_records()): V and gc are first read by the assembly / the PCG preparation of the trial
+        if (relposes()) launch_relpose(true, go ? 1 : 0, go);
         if (kind == BA_MOREQR) { // m_solver.compute(J) + Q^T r, once per outer iteration (BacktrackLevMarqMore.h:288-291): the point blocks ...
             launch_elim_qr(d_scal.p + SC_ZERO, d_rec0.p, d_dinv0.p, d_tvec0.p, d_tri0.p, go, /*thin Q for J2bot*/ more_qr());
             if (more_qr() && (rc = launch_more_outer(go))) return rc; // ... and the dense QR of J2bot(lambda = 0); its part 2 follows where a collective may stand
@@ -709,6 +716,10 @@ template <typename T> struct Solver final : SolverBase {
         if (nred > 0)
             hipLaunchKernelGGL((k_schur_reduce<T>), dim3((unsigned)((nthr + 191) / 192) + post_blocks), dim3(192), 0, st, nred, d_red_pairs.p, D, ld,
                                d_pair_hi.p, d_pair_lo.p, d_pair_chunk_ptr.p, d_slab.p, d_V.p, d_gc.p, d_S.p, lamf, post_blocks, Dp, d_gcg.p, d_dxc.p);
+        // every block of this S is written: the constraints' cross blocks join it here, for a trial and for the covariance alike
+        if (relposes())
+            hipLaunchKernelGGL((k_relpose_schur<T>), dim3((unsigned)(((size_t)n_rp * 36 + 255) / 256)), dim3(256), 0, st, n_rp, (const int *)d_rp_pair.p,
+                               (const T *)d_rp_rec.p, ld, d_S.p);
     }
 
     // ---- distributed factor (BA_DIST_FACTOR=1, sharded LDL^T symbols; SURVEY 8e "consider distributing K6" -- FUNCTIONAL, unmeasured: this
@@ -942,6 +953,10 @@ template <typename T> struct Solver final : SolverBase {
                                d_obs_pt.p, d_rec.p, Ml, d_pcg_w.p, d_dslab.p, d_pcg.p);
         hipLaunchKernelGGL((k_pcg_cam<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
                            d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gc, d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p);
+        if (relposes()) // (+ the constraints' cross blocks: y and the block partials, directly behind)
+            hipLaunchKernelGGL((k_pcg_relpose<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, relpose_csr(), (const T *)d_pcg_z.p, (const T *)d_pcg_p.p,
+                               (const T *)d_dxc.p, (const T *)d_pcg_b.p, (const double *)pcg_part_rz(), pcg_gc, d_pcg_y.p,
+                               FINAL ? pcg_part_res() : pcg_part_py(), (const ba_pcg_dev *)d_pcg.p);
     }
     // segment B's solve: pcg_max_iter iterations of four launches (the ones behind convergence return at once), the product S x of the
     // step and the statistics.  The solution is d_dxc, where launch_backsub_retract reads it.
@@ -995,7 +1010,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs) + prior_bytes();
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs) + prior_bytes() + relpose_bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1329,7 +1344,7 @@ template <typename T> struct Solver final : SolverBase {
             if ((rc = nid.upload(hid)) || (rc = nx0.upload(hx)) || (rc = ninfo.upload(hi))) { (void)hipGetLastError(); return rc; }
         }
         if (gp_new != gP) {
-            if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gp_new)) || (rc = npm.alloc((size_t)gM + gp_new)) ||
+            if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gp_new + 2 * (size_t)gR)) || (rc = npm.alloc((size_t)gM + gp_new)) ||
                 (rc = npr.alloc(3 * (size_t)gp_new))) { (void)hipGetLastError(); return rc; }
             HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
             HIPCHK(hipMemset(npm.p, 0, sizeof(T) * npm.n));
@@ -1363,10 +1378,114 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
 
+    // ---- relative-pose constraints (ba_solver_set_relative_poses; ba_relpose.hip.h) -------------------------------
+    // The lists, the per-constraint records and the CSR of every camera's incident constraints (built here, list order); the block
+    // partials of k_relpose live behind the priors' in d_part_e (2 gR).  No constraint: no buffer, gR = 0, not one launch more.
+    DevBuf<int> d_rp_pair, d_rp_ptr, d_rp_inc;
+    DevBuf<T> d_rp_R0, d_rp_t0, d_rp_Lr, d_rp_Lt, d_rp_rec, d_part_rp; // d_part_rp: [2][gR] energies of the last linearisation
+    int n_rp = 0, gR = 0;
+    bool relposes() const { return n_rp > 0; }
+    size_t relpose_bytes() const
+    {
+        return bytes_of(d_rp_pair) + bytes_of(d_rp_ptr) + bytes_of(d_rp_inc) + bytes_of(d_rp_R0) + bytes_of(d_rp_t0) + bytes_of(d_rp_Lr) +
+               bytes_of(d_rp_Lt) + bytes_of(d_rp_rec) + bytes_of(d_part_rp);
+    }
+    ba_relpose_csr<T> relpose_csr() const { return ba_relpose_csr<T>{d_rp_ptr.p, d_rp_inc.p, d_rp_pair.p, d_rp_rec.p}; }
+    // lin: the linearisation part (records, then the gather into V / gc of the state `which`); else the energy at xTest alone
+    void launch_relpose(bool lin, int which, const int *go)
+    {
+        ba_relpose_args<T> ra{n_rp, d_rp_pair.p, d_rp_R0.p, d_rp_t0.p, d_rp_Lr.p, d_rp_Lt.p};
+#define BA_RELPOSE(L, M) hipLaunchKernelGGL((k_relpose<T, L, M>), dim3(gR), dim3(256), 0, st, ra, N, (const T *)d_cam[which].p, d_rp_rec.p, \
+                                            d_part_e.p + gE + 3 * gP, d_part_rp.p, go, (const unsigned short *)d_cmask.p)
+        if (!lin) { BA_RELPOSE(false, false); return; }
+        if (masked && d_cmask.p) BA_RELPOSE(true, true);
+        else BA_RELPOSE(true, false);
+#undef BA_RELPOSE
+        hipLaunchKernelGGL((k_relpose_gather<T>), dim3((unsigned)(((size_t)N * BA_RP_ENT + 255) / 256)), dim3(256), 0, st, N, relpose_csr(), d_V.p, d_gc.p, go);
+    }
+    int set_relposes(int n, const int *pairs, const double *R0, const double *t0, const double *Lr, const double *Lt) override
+    {
+        if (!chol_elim() || sharded() || n < 0 || (n > 0 && (!pairs || !R0 || !t0 || !Lr || !Lt))) return BA_ERR_ARG;
+        {
+            std::vector<long long> seen;
+            seen.reserve((size_t)n);
+            for (int q = 0; q < n; q++) {
+                const int a = pairs[2 * q], b = pairs[2 * q + 1];
+                if (a < 0 || b < 0 || a >= N || b >= N || a == b) return BA_ERR_ARG;
+                seen.push_back((long long)std::max(a, b) * N + std::min(a, b));
+            }
+            std::sort(seen.begin(), seen.end());
+            if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return BA_ERR_ARG; // (an unordered pair listed twice)
+        }
+        auto finite = [](const double *v, size_t cnt) {
+            for (size_t q = 0; q < cnt; q++)
+                if (!std::isfinite(v[q]) || !std::isfinite((T)v[q])) return false;
+            return true;
+        };
+        if (n > 0 && !(finite(R0, (size_t)9 * n) && finite(t0, (size_t)3 * n) && finite(Lr, (size_t)9 * n) && finite(Lt, (size_t)9 * n))) return BA_ERR_ARG;
+        for (int q = 0; q < n; q++) { // R0 a rotation
+            const double *R = R0 + 9 * (size_t)q;
+            double dev = 0;
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++)
+                    dev = std::max(dev, std::fabs(R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0)));
+            const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+            if (!(dev <= 1e-6) || !(det > 0)) return BA_ERR_ARG;
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        const int gr_new = (n + 255) / 256;
+        int rc;
+        // everything that can fail first: the solver is unchanged behind an error
+        DevBuf<int> npair, nptr, ninc;
+        DevBuf<T> nR0, nt0, nLr, nLt, nrec, npe, npr;
+        if (n > 0) {
+            std::vector<int> hp(pairs, pairs + 2 * (size_t)n), ptr((size_t)N + 1, 0), inc(2 * (size_t)n);
+            for (int q = 0; q < 2 * n; q++) ptr[hp[q] + 1]++;
+            for (int a = 0; a < N; a++) ptr[a + 1] += ptr[a];
+            std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+            for (int q = 0; q < n; q++) { inc[fill[hp[2 * q]]++] = 2 * q; inc[fill[hp[2 * q + 1]]++] = 2 * q + 1; }
+            auto conv = [](const double *v, size_t cnt) { std::vector<T> h(cnt); for (size_t q = 0; q < cnt; q++) h[q] = (T)v[q]; return h; };
+            if ((rc = npair.upload(hp)) || (rc = nptr.upload(ptr)) || (rc = ninc.upload(inc)) || (rc = nR0.upload(conv(R0, (size_t)9 * n))) ||
+                (rc = nt0.upload(conv(t0, (size_t)3 * n))) || (rc = nLr.upload(conv(Lr, (size_t)9 * n))) || (rc = nLt.upload(conv(Lt, (size_t)9 * n))) ||
+                (rc = nrec.alloc((size_t)BA_RP_REC * n))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(nrec.p, 0, sizeof(T) * nrec.n));
+        }
+        if (gr_new != gR) {
+            if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gP + 2 * (size_t)gr_new)) || (rc = npr.alloc(2 * (size_t)gr_new))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
+            if (npr.p) HIPCHK(hipMemset(npr.p, 0, sizeof(T) * npr.n));
+            std::swap(d_part_e.p, npe.p); std::swap(d_part_e.n, npe.n);
+            std::swap(d_part_rp.p, npr.p); std::swap(d_part_rp.n, npr.n);
+            gR = gr_new;
+        }
+#define BA_SWAP(A, B) std::swap(A.p, B.p); std::swap(A.n, B.n)
+        BA_SWAP(d_rp_pair, npair); BA_SWAP(d_rp_ptr, nptr); BA_SWAP(d_rp_inc, ninc); BA_SWAP(d_rp_R0, nR0); BA_SWAP(d_rp_t0, nt0);
+        BA_SWAP(d_rp_Lr, nLr); BA_SWAP(d_rp_Lt, nLt); BA_SWAP(d_rp_rec, nrec);
+#undef BA_SWAP
+        n_rp = n;
+        return model_changed(); // (the old buffers leave with the locals)
+    }
+    // {sum |e_r|^2, sum |e_t|^2} of the last linearisation's partials, in index order
+    int relpose_energy(double *out2) override
+    {
+        if (!chol_elim() || sharded() || !have_lin || mask_pending) return BA_ERR_ARG;
+        out2[0] = out2[1] = 0.0;
+        if (!relposes()) return BA_OK;
+        std::vector<T> h;
+        int rc;
+        if ((rc = dl(d_part_rp.p, 2 * (size_t)gR, h))) return rc;
+        for (int q = 0; q < 2; q++) {
+            T a = 0;
+            for (int b = 0; b < gR; b++) a += h[(size_t)q * gR + b];
+            out2[q] = (double)a;
+        }
+        return BA_OK;
+    }
+
     ba_red_jobs test_energy_jobs() const
     {
         ba_red_jobs jobs{};
-        jobs.j[0] = {d_part_e.p, gE + 3 * gP, 0, SC_ETEST}; // (gP = 0 without priors)
+        jobs.j[0] = {d_part_e.p, gE + 3 * gP + 2 * gR, 0, SC_ETEST}; // (gP = 0 without priors, gR = 0 without constraints)
         jobs.j[1] = {d_part_bs.p, gB, 0, SC_RHO_P};
         jobs.j[2] = {d_part_bs.p + gB, gB, 0, SC_DN_P};
         return jobs;
@@ -1376,6 +1495,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         launch_eval(false, 1);
         if (priors()) launch_prior(false, 1, nullptr);
+        if (relposes()) launch_relpose(false, 1, nullptr);
         if (reduce) hipLaunchKernelGGL((k_reduce_scalars<T>), dim3(3), dim3(256), 0, st, test_energy_jobs(), d_scal.p, (const int *)nullptr);
     }
 
@@ -1980,7 +2100,7 @@ template <typename T> struct Solver final : SolverBase {
         for (int k = 0; k < reps; k++) {
             switch (phase) {
             case 0: launch_eval(false, 0); break;
-            case 1: launch_eval(true, 0); launch_grad(); if (priors()) launch_prior(true, 0, nullptr); break;
+            case 1: launch_eval(true, 0); launch_grad(); if (priors()) launch_prior(true, 0, nullptr); if (relposes()) launch_relpose(true, 0, nullptr); break;
             case 2: launch_eliminate(); break;
             case 3: launch_assemble(); break; // (QRKIT: J2bot instead of S)
             case 4:
@@ -1994,6 +2114,7 @@ template <typename T> struct Solver final : SolverBase {
                 launch_eval(true, 0, nullptr, false, true);
                 launch_grad(nullptr, nullptr, !fuse);
                 if (priors()) launch_prior(true, 0, nullptr);
+                if (relposes()) launch_relpose(true, 0, nullptr);
                 break;
             case 6: // dense factorisation only (k_ldlt_panel + k_ldlt_step / k_ldlt_update; QRKIT: the Householder QR + solve): events around it, per rep
             case 7: // backward sweep only (k_ldlt_backflow; QRKIT: nothing, the solve is part of 6)
@@ -2179,6 +2300,12 @@ int ba_solver_set_intrinsics_priors(ba_solver *s, int n, const int *cam_ids, con
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_priors(2, n, cam_ids, x0, w);
 }
 int ba_solver_prior_energy(ba_solver *s, double *out3) { return !(s && out3) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->prior_energy(out3); }
+int ba_solver_set_relative_poses(ba_solver *s, int n, const int *cam_pairs, const double *R0, const double *t0, const double *sqrt_info_rot,
+                                 const double *sqrt_info_trans)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_relposes(n, cam_pairs, R0, t0, sqrt_info_rot, sqrt_info_trans);
+}
+int ba_solver_relative_pose_energy(ba_solver *s, double *out2) { return !(s && out2) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->relpose_energy(out2); }
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

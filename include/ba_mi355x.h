@@ -405,6 +405,38 @@ int ba_solver_set_intrinsics_priors(ba_solver *s, int n, const int *cam_ids, con
  * priors).  BA_ERR_ARG: another kind, sharded, no linearisation, or a model set since the last one. */
 int ba_solver_prior_energy(ba_solver *s, double *out3);
 
+/* ---- Relative-pose constraints between camera pairs (no reference counterpart; Ceres' residual blocks on two pose blocks, g2o's
+ * EdgeSE3): a rig's calibrated extrinsic, odometry between consecutive frames, a turntable's known rotation ------------------------- */
+
+/* For a constraint between cameras a and b (x_cam = R X + T) the pose of a's frame seen from b's is
+ *   R_ab = R_b R_a^T,   t_ab = T_b - R_ab T_a          (x_b = R_ab x_a + t_ab; both invariant under a rigid motion of the world)
+ * and the constraint adds six rows to J, without a robust loss, like the priors:
+ *   e_t = L_t (t_ab - t0)                              3 rows
+ *   e_r = L_r phi,  phi = Log(R_ab R0^T)               3 rows (rotation vector, |phi| < pi; its accuracy degrades like eps / (pi - |phi|))
+ * L_t = sqrt_info_trans, L_r = sqrt_info_rot: any real 3 x 3, row-major; all zero: no rows of that kind.  The solver minimises
+ *   sum_o rho(|r_o|^2) + sum_priors |e|^2 + sum_constraints (|e_t|^2 + |e_r|^2).
+ * Jacobian on the pose columns (T, omega) of the two cameras for the retraction T + dT, R <- Rodrigues(d omega) R (intrinsics columns 0),
+ * with u = R_ab T_a and Jl^-1 = I - [phi]x / 2 + c [phi]x^2, c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta):
+ *   d e_t / d(T_a, omega_a) = L_t [-R_ab | -R_ab [T_a]x]      d e_t / d(T_b, omega_b) = L_t [I | [u]x]
+ *   d e_r / d(T_a, omega_a) = L_r [  0   | -Jl^-1 R_ab  ]      d e_r / d(T_b, omega_b) = L_r [0 | Jl^-1]
+ * These rows enter J'J (the 9 x 9 blocks of both cameras AND the block between them -- also for a pair that shares no point), g = -J'e
+ * (BA_GET_GRAD), the energy that ba_solver_linearize, ba_solver_try_step and the LM table report, lambda0, rho and the stop tests, S
+ * (BA_GET_S with ba_solver_keep_intermediates), rhs, BA_ITERSCHUR's operator and preconditioner, and the covariance.  BA_GET_RESIDUALS /
+ * BA_GET_JC / BA_GET_JP stay the 2K observation rows.  With ba_solver_set_constant the columns of a fixed parameter are zero; a
+ * constraint whose two poses are fixed is a constant in the energy.  May be combined with priors, any loss and weights.
+ * cam_pairs: 2n indices (a, b) of the PROBLEM; R0: 9n row-major; t0: 3n; sqrt_info_rot, sqrt_info_trans: 9n each; copied.  n = 0 removes
+ * the constraints and the solver runs the path without them again, bit for bit.  A call takes effect at the next ba_solver_linearize or
+ * ba_minimize; a ba_solver_try_step before that returns BA_ERR_ARG, and a computed covariance becomes stale.
+ * BA_CHOLESKY and BA_ITERSCHUR, BA_F64 and BA_F32, shard_world == 1.
+ * BA_ERR_ARG, the solver unchanged: another kind (the QR kinds would need rows that span two camera blocks in J2bot: not built), a
+ * sharded solver (not built), a == b or an index out of range, an unordered pair listed twice, a value that is not finite (in the
+ * solver's scalar type), an R0 that is no rotation (max |R0 R0^T - I| > 1e-6 or det <= 0), n < 0, a NULL array with n > 0. */
+int ba_solver_set_relative_poses(ba_solver *s, int n, const int *cam_pairs /* 2n: a, b */, const double *R0 /* 9n row-major */,
+                                 const double *t0 /* 3n */, const double *sqrt_info_rot /* 9n */, const double *sqrt_info_trans /* 9n */);
+/* out2 = {sum |e_r|^2, sum |e_t|^2} at x of the last linearisation (zeros without constraints).  BA_ERR_ARG: another kind, sharded, no
+ * linearisation, or a model set since the last one. */
+int ba_solver_relative_pose_energy(ba_solver *s, double *out2);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);

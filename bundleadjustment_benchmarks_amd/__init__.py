@@ -25,6 +25,9 @@ FIX_T, FIX_OMEGA, FIX_POSE, FIX_INTRINSICS, FIX_CAMERA = 0x007, 0x038, 0x03F, 0x
 # ba_solver_set_loss: rho(s) of the weighted squared reprojection error s (include/ba_mi355x.h); a new solver is (LOSS_REFERENCE, 0.5)
 LOSS_REFERENCE, LOSS_TRIVIAL, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2, 3
 
+# ba_solver_set_preconditioner (ITERSCHUR): block Jacobi, or block Jacobi + the cross blocks of a spanning forest of the constraints
+PRECOND_BLOCK_JACOBI, PRECOND_CONSTRAINT_FOREST = 0, 1
+
 (GET_RESIDUALS, GET_JC, GET_JP, GET_GRAD, GET_S, GET_RHS, GET_DX, GET_CAMS, GET_POINTS, GET_CAMS_TEST,
  GET_POINTS_TEST) = range(11)
 
@@ -41,6 +44,7 @@ EXPORTS = [
     "ba_solver_set_loss", "ba_solver_set_obs_weights",
     "ba_solver_set_point_priors", "ba_solver_set_centre_priors", "ba_solver_set_intrinsics_priors", "ba_solver_prior_energy",
     "ba_solver_set_relative_poses", "ba_solver_relative_pose_energy",
+    "ba_solver_set_preconditioner", "ba_solver_preconditioner_info", "ba_relpose_forest_plan",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -143,6 +147,9 @@ def lib():
         L.ba_solver_prior_energy.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_relative_poses.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.ba_solver_relative_pose_energy.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_set_preconditioner.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ba_solver_preconditioner_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_relpose_forest_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -340,6 +347,20 @@ class Solver:
         """ITERSCHUR: at most max_iter PCG iterations per trial, stop at |r| <= rel_tol |rhs|."""
         _chk(lib().ba_solver_set_pcg(self._h, int(max_iter), float(rel_tol)), "ba_solver_set_pcg")
 
+    def set_preconditioner(self, kind, max_tree=0):
+        """ITERSCHUR: PRECOND_BLOCK_JACOBI (a new solver's) or PRECOND_CONSTRAINT_FOREST with at most max_tree cameras per tree (0: the
+        library's default)."""
+        _chk(lib().ba_solver_set_preconditioner(self._h, int(kind), int(max_tree)), "ba_solver_set_preconditioner")
+
+    def preconditioner_info(self):
+        """dict(kind, max_tree, trees, kept, dropped, largest_tree, fallback_trees): the forest in force and the trees of the last solve
+        that fell back to block Jacobi."""
+        out, fb = np.zeros(6, np.int64), C.c_int(0)
+        _chk(lib().ba_solver_preconditioner_info(self._h, _p(out), C.byref(fb)), "ba_solver_preconditioner_info")
+        d = dict(zip(("kind", "max_tree", "trees", "kept", "dropped", "largest_tree"), (int(v) for v in out)))
+        d["fallback_trees"] = int(fb.value)
+        return d
+
     def set_constant(self, cam_mask=None, pt_fixed=None):
         """Hold parameters constant from the next linearize() / minimize() on: cam_mask uint16[N] (FIX_* bits), pt_fixed bool / uint8[M]
         of the problem (None: nothing of that kind; both None or all zero: the unmasked solver)."""
@@ -507,6 +528,17 @@ class Solver:
 
 
 COMM_ID_BYTES = 128
+
+
+def forest_plan(N, pairs, max_tree):
+    """ba_relpose_forest_plan (host only): dict(parent [N], via [N], order [N], kept [n] bool) of the spanning forest that
+    PRECOND_CONSTRAINT_FOREST builds from the constraint list `pairs` ([n, 2]) with at most max_tree cameras per tree."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    n = len(pairs)
+    parent, via, order = (np.zeros(max(int(N), 0), np.int32) for _ in range(3))
+    kept = np.zeros(n, np.uint8)
+    _chk(lib().ba_relpose_forest_plan(int(N), n, _p(pairs), int(max_tree), _p(parent), _p(via), _p(order), _p(kept)), "ba_relpose_forest_plan")
+    return dict(parent=parent, via=via, order=order, kept=kept.astype(bool))
 
 
 def relative_pose(cam15, a, b):

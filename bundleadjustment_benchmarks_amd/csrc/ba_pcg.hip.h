@@ -21,6 +21,11 @@
 // block partials itself (same order, same bits), the partials of r'z kept for the last three iterations (k writes slot k + 1, reads
 // k and k - 1).  p_k = z_k + beta_k p_{k-1} is formed on the fly by the consumers of iteration k and stored by its last launch.
 // Behind the iterations one more product S x gives the true residual |rhs - S x| / |rhs| of the step (k_pcg_finish records it).
+//
+// BA_PRECOND_CONSTRAINT_FOREST (ba_pcg_forest.hip.h): the cameras of the forest's trees (in_tree) get their z from k_pcg_forest_apply,
+// launched behind k_pcg_prec_inv and behind every k_pcg_update, which leave those cameras' z and r'z alone (FOREST instantiations).  The
+// trees' partials of r'z follow the gc per-camera ones, so the list of r'z has gz = gc + trees entries per slot (gz = gc without a
+// forest) while |r|^2 keeps gc.
 #ifndef BA_PCG_HIP_H
 #define BA_PCG_HIP_H
 
@@ -37,6 +42,8 @@ struct ba_pcg_dev {
     int last_iters, last_converged;
     double last_rel_residual;
 };
+
+#include "ba_pcg_forest.hip.h" /* (needs ba_pcg_dev) */
 
 // the block's fixed-order sum of n fp64 partials, returned to every thread (all 256 threads must call it)
 __device__ __forceinline__ double ba_pcg_sum(const double *__restrict__ a, int n, double *lds)
@@ -143,9 +150,10 @@ __global__ __launch_bounds__(256) void k_pcg_prec_reduce(int N, const int *__res
 // Per camera (one thread): B_a = L L^T in fp64 and Bm <- B_a^-1 = L^-T L^-1 in place (a block that is not positive definite in
 // working precision -- fp32 at a tiny lambda -- falls back to the inverse of its diagonal); x_0 = 0, r_0 = rhs, z_0 = M^-1 r_0,
 // p_{-1} = 0; the block partials of r_0'z_0 and |r_0|^2 into slot 0.
-template <typename T>
+template <typename T, bool FOREST = false>
 __global__ __launch_bounds__(256) void k_pcg_prec_inv(int N, T *__restrict__ Bm, const T *__restrict__ rhs, T *__restrict__ x, T *__restrict__ r,
-                                                      T *__restrict__ z, T *__restrict__ p, double *__restrict__ part_rz, double *__restrict__ part_rr)
+                                                      T *__restrict__ z, T *__restrict__ p, double *__restrict__ part_rz, double *__restrict__ part_rr,
+                                                      const unsigned char *__restrict__ in_tree)
 {
     __shared__ double red[4];
     const int a = blockIdx.x * 256 + threadIdx.x;
@@ -221,7 +229,7 @@ __global__ __launch_bounds__(256) void k_pcg_prec_inv(int N, T *__restrict__ Bm,
             for (int k = 0; k < 9; k++) zi += Mt[9 * i + k] * b[k];
             const size_t o = 9 * (size_t)a + i;
             x[o] = 0; r[o] = b[i]; z[o] = zi; p[o] = 0;
-            rz += (double)b[i] * (double)zi;
+            if (!(FOREST && in_tree[a])) rz += (double)b[i] * (double)zi;
             rr += (double)b[i] * (double)b[i];
         }
     }
@@ -240,11 +248,11 @@ __global__ __launch_bounds__(256) void k_pcg_start(const double *__restrict__ pa
 
 // ---- per iteration k (FINAL: the product S x behind the last iteration) -----------------------------------------------------------------
 // beta_k = (r_k'z_k) / (r_{k-1}'z_{k-1}) from the block partials (0 at k = 0); every block sums them itself
-__device__ __forceinline__ double ba_pcg_beta(int k, const double *__restrict__ part_rz, int gc, double *red)
+__device__ __forceinline__ double ba_pcg_beta(int k, const double *__restrict__ part_rz, int gz, double *red)
 {
     if (k == 0) return 0.0;
-    const double rzk = ba_pcg_sum(part_rz + (size_t)ba_pcg_slot(k) * gc, gc, red);
-    const double rzm = ba_pcg_sum(part_rz + (size_t)ba_pcg_slot(k + 2) * gc, gc, red);
+    const double rzk = ba_pcg_sum(part_rz + (size_t)ba_pcg_slot(k) * gz, gz, red);
+    const double rzm = ba_pcg_sum(part_rz + (size_t)ba_pcg_slot(k + 2) * gz, gz, red);
     return rzk / rzm;
 }
 
@@ -254,7 +262,7 @@ template <typename T, int LPP, bool FINAL>
 __global__ __launch_bounds__(256) void k_pcg_point(int k, int Ml, const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,
                                                    const T *__restrict__ rec, const T *__restrict__ dinv, const T *__restrict__ z,
                                                    const T *__restrict__ p, const T *__restrict__ x, const double *__restrict__ part_rz,
-                                                   const double *__restrict__ part_rr, int gc, double tol2, ba_pcg_dev *__restrict__ pcg,
+                                                   const double *__restrict__ part_rr, int gc, int gz, double tol2, ba_pcg_dev *__restrict__ pcg,
                                                    T *__restrict__ w)
 {
     __shared__ double red[4];
@@ -266,7 +274,7 @@ __global__ __launch_bounds__(256) void k_pcg_point(int k, int Ml, const int *__r
             if (blockIdx.x == 0 && threadIdx.x == 0) { pcg->done = 1; pcg->iters = k; }
             return;
         }
-        beta = (T)ba_pcg_beta(k, part_rz, gc, red);
+        beta = (T)ba_pcg_beta(k, part_rz, gz, red);
     }
     const int gid = (blockIdx.x * 256 + threadIdx.x) / LPP, lg = threadIdx.x % LPP;
     const bool ok = gid < Ml;
@@ -327,14 +335,14 @@ template <typename T, bool FINAL>
 __global__ __launch_bounds__(256) void k_pcg_cam(int k, int N, const int *__restrict__ cam_dchunk_ptr, const T *__restrict__ slab,
                                                  const T *__restrict__ V, const T *__restrict__ lam, const T *__restrict__ z,
                                                  const T *__restrict__ p, const T *__restrict__ x, const T *__restrict__ rhs,
-                                                 const double *__restrict__ part_rz, int gc, T *__restrict__ y, double *__restrict__ part,
+                                                 const double *__restrict__ part_rz, int gz, T *__restrict__ y, double *__restrict__ part,
                                                  const ba_pcg_dev *__restrict__ pcg)
 {
     __shared__ double red[4];
     T beta = 0;
     if (!FINAL) {
         if (pcg->done) return;
-        beta = (T)ba_pcg_beta(k, part_rz, gc, red);
+        beta = (T)ba_pcg_beta(k, part_rz, gz, red);
     }
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t a = idx / 9;
@@ -380,13 +388,13 @@ __global__ __launch_bounds__(256) void k_pcg_cam(int k, int N, const int *__rest
 template <typename T, bool FINAL>
 __global__ __launch_bounds__(256) void k_pcg_relpose(int k, int N, ba_relpose_csr<T> cs, const T *__restrict__ z, const T *__restrict__ p,
                                                      const T *__restrict__ x, const T *__restrict__ rhs, const double *__restrict__ part_rz,
-                                                     int gc, T *__restrict__ y, double *__restrict__ part, const ba_pcg_dev *__restrict__ pcg)
+                                                     int gz, T *__restrict__ y, double *__restrict__ part, const ba_pcg_dev *__restrict__ pcg)
 {
     __shared__ double red[4];
     T beta = 0;
     if (!FINAL) {
         if (pcg->done) return;
-        beta = (T)ba_pcg_beta(k, part_rz, gc, red);
+        beta = (T)ba_pcg_beta(k, part_rz, gz, red);
     }
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t a = idx / 9;
@@ -405,16 +413,16 @@ __global__ __launch_bounds__(256) void k_pcg_relpose(int k, int N, ba_relpose_cs
 
 // Per camera (one thread): alpha_k = r_k'z_k / p_k'S p_k; x += alpha p_k; r -= alpha S p_k; p <- p_k; z = M^-1 r; the block partials of
 // r_{k+1}'z_{k+1} and |r_{k+1}|^2 into slot k + 1
-template <typename T>
+template <typename T, bool FOREST = false>
 __global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__restrict__ Minv, const T *__restrict__ y, T *__restrict__ z,
                                                     T *__restrict__ p, T *__restrict__ x, T *__restrict__ r, double *__restrict__ part_rz,
-                                                    double *__restrict__ part_rr, const double *__restrict__ part_py, int gc, int gq,
-                                                    const ba_pcg_dev *__restrict__ pcg)
+                                                    double *__restrict__ part_rr, const double *__restrict__ part_py, int gc, int gz, int gq,
+                                                    const ba_pcg_dev *__restrict__ pcg, const unsigned char *__restrict__ in_tree)
 {
     __shared__ double red[4];
     if (pcg->done) return;
-    const double rzk = ba_pcg_sum(part_rz + (size_t)ba_pcg_slot(k) * gc, gc, red);
-    const T beta = (T)ba_pcg_beta(k, part_rz, gc, red);
+    const double rzk = ba_pcg_sum(part_rz + (size_t)ba_pcg_slot(k) * gz, gz, red);
+    const T beta = (T)ba_pcg_beta(k, part_rz, gz, red);
     const double py = ba_pcg_sum(part_py, gq, red);
     const T alpha = (T)(rzk / py);
     const int a = blockIdx.x * 256 + threadIdx.x;
@@ -431,20 +439,23 @@ __global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__res
             r[o + q] = rv[q];
         }
         const T *Mi = Minv + (size_t)a * 81;
+        const bool tree = FOREST && in_tree[a]; // (z and r'z of this camera: k_pcg_forest_apply, directly behind)
 #pragma unroll
         for (int i = 0; i < 9; i++) {
             T zi = 0;
 #pragma unroll
             for (int q = 0; q < 9; q++) zi += Mi[9 * i + q] * rv[q];
-            z[o + i] = zi;
-            rz += (double)rv[i] * (double)zi;
+            if (!tree) {
+                z[o + i] = zi;
+                rz += (double)rv[i] * (double)zi;
+            }
             rr += (double)rv[i] * (double)rv[i];
         }
     }
     rz = block_reduce<double, false>(rz, red);
     rr = block_reduce<double, false>(rr, red);
     if (threadIdx.x == 0) {
-        part_rz[(size_t)ba_pcg_slot(k + 1) * gc + blockIdx.x] = rz;
+        part_rz[(size_t)ba_pcg_slot(k + 1) * gz + blockIdx.x] = rz;
         part_rr[(size_t)ba_pcg_slot(k + 1) * gc + blockIdx.x] = rr;
     }
 }

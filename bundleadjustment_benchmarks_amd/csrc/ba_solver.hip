@@ -96,6 +96,8 @@ struct SolverBase {
     virtual int selftest(int which) = 0;
     virtual int set_pcg(int max_iter, double rel_tol) = 0;
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
+    virtual int set_precond(int kind, int max_tree) = 0;
+    virtual int precond_info(long long *out6, int *fallback_trees) = 0;
     virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
     virtual int set_loss(int kind, double scale) = 0;
     virtual int set_obs_weights(const double *w) = 0;
@@ -923,10 +925,114 @@ template <typename T> struct Solver final : SolverBase {
     int pcg_gc = 1, pcg_gq = 1; // blocks of the per-camera and per-(camera, row) launches
     int pcg_max_iter = BA_PCG_MAX_ITER_DEFAULT;
     double pcg_rel_tol = BA_PCG_REL_TOL_DEFAULT;
-    double *pcg_part_rz() const { return d_pcg_part.p; }
-    double *pcg_part_rr() const { return d_pcg_part.p + (size_t)3 * pcg_gc; }
-    double *pcg_part_py() const { return d_pcg_part.p + (size_t)6 * pcg_gc; }
-    double *pcg_part_res() const { return d_pcg_part.p + (size_t)6 * pcg_gc + pcg_gq; }
+    // (with a forest the list of r'z is longer by one partial per tree and the four lists live in the forest's own buffer)
+    int pcg_gz() const { return pcg_gc + (forest_on() ? fo.ntrees : 0); }
+    double *pcg_part_rz() const { return forest_on() ? fo.part.p : d_pcg_part.p; }
+    double *pcg_part_rr() const { return pcg_part_rz() + (size_t)3 * pcg_gz(); }
+    double *pcg_part_py() const { return pcg_part_rr() + (size_t)3 * pcg_gc; }
+    double *pcg_part_res() const { return pcg_part_py() + pcg_gq; }
+
+    // ---- BA_PRECOND_CONSTRAINT_FOREST (ba_pcg_forest.hip.h) -------------------------------------------------------
+    // The lists of ba_relpose_forest_plan in elimination order, tree after tree, built by set_precond / set_relposes.  Without a kept
+    // constraint there is no buffer and not one launch or argument differs from block Jacobi.
+    struct Forest {
+        DevBuf<int> tree_ptr, node_cam, node_par, node_rec, bad;
+        DevBuf<unsigned char> in_tree;
+        DevBuf<T> fac, u;
+        DevBuf<double> work, part;
+        int ntrees = 0, nodes = 0, kept = 0, dropped = 0, largest = 0;
+        void swap(Forest &o)
+        {
+#define BA_SWAP(A) std::swap(A.p, o.A.p); std::swap(A.n, o.A.n)
+            BA_SWAP(tree_ptr); BA_SWAP(node_cam); BA_SWAP(node_par); BA_SWAP(node_rec); BA_SWAP(bad); BA_SWAP(in_tree); BA_SWAP(fac); BA_SWAP(u);
+            BA_SWAP(work); BA_SWAP(part);
+#undef BA_SWAP
+            std::swap(ntrees, o.ntrees); std::swap(nodes, o.nodes); std::swap(kept, o.kept); std::swap(dropped, o.dropped); std::swap(largest, o.largest);
+        }
+        size_t bytes() const
+        {
+            return bytes_of(tree_ptr) + bytes_of(node_cam) + bytes_of(node_par) + bytes_of(node_rec) + bytes_of(bad) + bytes_of(in_tree) + bytes_of(fac) +
+                   bytes_of(u) + bytes_of(work) + bytes_of(part);
+        }
+    } fo;
+    int precond_kind = BA_PRECOND_BLOCK_JACOBI, precond_max_tree = BA_PCG_MAX_TREE_DEFAULT;
+    std::vector<int> h_rp_pair; // the constraint list as set (host copy for the forest)
+    bool forest_on() const { return precond_kind == BA_PRECOND_CONSTRAINT_FOREST && fo.ntrees > 0; }
+    ba_forest_dev<T> forest_dev() const
+    {
+        return ba_forest_dev<T>{fo.tree_ptr.p, fo.node_cam.p, fo.node_par.p, fo.node_rec.p, fo.fac.p, fo.work.p, fo.u.p, fo.bad.p};
+    }
+    // the forest of `pairs` under (kind, max_tree) into `out`; everything that can fail, nothing of the solver touched
+    int build_forest(const std::vector<int> &pairs, int kind, int max_tree, Forest &out) const
+    {
+        const int n = (int)(pairs.size() / 2);
+        out.dropped = n;
+        out.largest = N > 0 ? 1 : 0;
+        if (kind != BA_PRECOND_CONSTRAINT_FOREST || n == 0 || max_tree < 2) return BA_OK;
+        std::vector<int> parent((size_t)N), via((size_t)N), order((size_t)N);
+        std::vector<unsigned char> kept((size_t)n);
+        int rc = ba_relpose_forest_plan(N, n, pairs.data(), max_tree, parent.data(), via.data(), order.data(), kept.data());
+        if (rc) return rc;
+        for (int q = 0; q < n; q++) out.kept += kept[q];
+        out.dropped = n - out.kept;
+        if (out.kept == 0) return BA_OK;
+        std::vector<unsigned char> in_tree((size_t)N, 0);
+        for (int a = 0; a < N; a++)
+            if (parent[a] >= 0) { in_tree[a] = 1; in_tree[parent[a]] = 1; }
+        std::vector<int> pos((size_t)N, -1), tree_ptr(1, 0), node_cam, node_par, node_rec;
+        for (int k = 0; k < N && in_tree[order[k]]; k++) pos[order[k]] = k; // (the lone cameras are last)
+        for (int k = 0; k < N && in_tree[order[k]]; k++) {
+            const int c = order[k];
+            node_cam.push_back(c);
+            node_par.push_back(parent[c] >= 0 ? pos[parent[c]] : -1);
+            node_rec.push_back(parent[c] >= 0 ? 2 * via[c] + (pairs[2 * (size_t)via[c]] == c ? 0 : 1) : -1);
+            if (parent[c] < 0) { // the root ends its tree
+                out.largest = std::max(out.largest, k + 1 - tree_ptr.back());
+                tree_ptr.push_back(k + 1);
+            }
+        }
+        out.ntrees = (int)tree_ptr.size() - 1;
+        out.nodes = (int)node_cam.size();
+        if ((rc = out.tree_ptr.upload(tree_ptr)) || (rc = out.node_cam.upload(node_cam)) || (rc = out.node_par.upload(node_par)) ||
+            (rc = out.node_rec.upload(node_rec)) || (rc = out.in_tree.upload(in_tree)) || (rc = out.bad.alloc((size_t)out.ntrees)) ||
+            (rc = out.fac.alloc((size_t)out.nodes * BA_FOREST_FAC)) || (rc = out.work.alloc((size_t)out.nodes * 81)) ||
+            (rc = out.u.alloc(out.largest > BA_FOREST_LDS ? (size_t)out.nodes * 9 : 0)) ||
+            (rc = out.part.alloc((size_t)3 * (pcg_gc + out.ntrees) + (size_t)3 * pcg_gc + 2 * (size_t)pcg_gq))) { (void)hipGetLastError(); return rc; }
+        HIPCHK(hipMemset(out.bad.p, 0, sizeof(int) * out.bad.n));
+        HIPCHK(hipMemset(out.part.p, 0, sizeof(double) * out.part.n));
+        return BA_OK;
+    }
+    int set_precond(int kind, int max_tree) override
+    {
+        if (!iterative() || (kind != BA_PRECOND_BLOCK_JACOBI && kind != BA_PRECOND_CONSTRAINT_FOREST) || max_tree < 0) return BA_ERR_ARG;
+        if (max_tree == 0) max_tree = BA_PCG_MAX_TREE_DEFAULT;
+        Forest nf;
+        int rc;
+        if ((rc = build_forest(h_rp_pair, kind, max_tree, nf))) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        fo.swap(nf);
+        precond_kind = kind; precond_max_tree = max_tree;
+        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl}) // (captured with the old launch sequence)
+            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        return BA_OK;
+    }
+    int precond_info(long long *out6, int *fallback_trees) override
+    {
+        if (!iterative()) return BA_ERR_ARG;
+        if (out6) {
+            out6[0] = precond_kind; out6[1] = precond_max_tree; out6[2] = fo.ntrees; out6[3] = fo.kept; out6[4] = fo.dropped; out6[5] = fo.largest;
+        }
+        if (fallback_trees) {
+            *fallback_trees = 0;
+            if (forest_on()) {
+                std::vector<int> h((size_t)fo.ntrees);
+                HIPCHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpy(h.data(), fo.bad.p, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+                for (int v : h) *fallback_trees += v;
+            }
+        }
+        return BA_OK;
+    }
 
     // segment A behind k_elim_chol: block-Jacobi preconditioner, reduced rhs, g_c for the retraction's rho terms, x_0 = 0 and the
     // recurrence's start (p_{-1} = 0, z_0, slot-0 partials, |rhs|^2)
@@ -937,8 +1043,15 @@ template <typename T> struct Solver final : SolverBase {
                                d_rec.p, d_tvec.p, Ml, d_dslab.p);
         hipLaunchKernelGGL((k_pcg_prec_reduce<T>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
                            d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, d_pcg_M.p, d_pcg_b.p, d_gcg.p);
-        hipLaunchKernelGGL((k_pcg_prec_inv<T>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
-                           pcg_part_rz(), pcg_part_rr());
+        if (forest_on()) { // the factor reads B_a in front of its inversion in place; z_0 and r_0'z_0 of the trees behind it
+            hipLaunchKernelGGL((k_pcg_forest_factor<T>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+            hipLaunchKernelGGL((k_pcg_prec_inv<T, true>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
+                               pcg_part_rz(), pcg_part_rr(), (const unsigned char *)fo.in_tree.p);
+            hipLaunchKernelGGL((k_pcg_forest_apply<T, true>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_r.p, d_pcg_z.p,
+                               pcg_part_rz() + pcg_gc, (const ba_pcg_dev *)d_pcg.p);
+        } else
+            hipLaunchKernelGGL((k_pcg_prec_inv<T>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
+                               pcg_part_rz(), pcg_part_rr(), (const unsigned char *)nullptr);
         hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(256), 0, st, pcg_part_rr(), pcg_gc, d_pcg.p);
     }
     // y = S v: the point pass, then the camera pass (chunk partials in d_dslab, then per camera)
@@ -947,15 +1060,15 @@ template <typename T> struct Solver final : SolverBase {
         const T *lam = d_scal.p + SC_LAMBDA;
         if (Ml > 0)
             hipLaunchKernelGGL((k_pcg_point<T, 8, FINAL>), dim3((unsigned)(((size_t)Ml * 8 + 255) / 256)), dim3(256), 0, st, k, Ml, d_pt_ptr.p, d_obs_cam.p,
-                               d_rec.p, d_dinv.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, pcg_part_rz(), pcg_part_rr(), pcg_gc, tol2, d_pcg.p, d_pcg_w.p);
+                               d_rec.p, d_dinv.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, pcg_part_rz(), pcg_part_rr(), pcg_gc, pcg_gz(), tol2, d_pcg.p, d_pcg_w.p);
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_cam_chunks<T, FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p,
                                d_obs_pt.p, d_rec.p, Ml, d_pcg_w.p, d_dslab.p, d_pcg.p);
         hipLaunchKernelGGL((k_pcg_cam<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
-                           d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gc, d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p);
+                           d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gz(), d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p);
         if (relposes()) // (+ the constraints' cross blocks: y and the block partials, directly behind)
             hipLaunchKernelGGL((k_pcg_relpose<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, relpose_csr(), (const T *)d_pcg_z.p, (const T *)d_pcg_p.p,
-                               (const T *)d_dxc.p, (const T *)d_pcg_b.p, (const double *)pcg_part_rz(), pcg_gc, d_pcg_y.p,
+                               (const T *)d_dxc.p, (const T *)d_pcg_b.p, (const double *)pcg_part_rz(), pcg_gz(), d_pcg_y.p,
                                FINAL ? pcg_part_res() : pcg_part_py(), (const ba_pcg_dev *)d_pcg.p);
     }
     // segment B's solve: pcg_max_iter iterations of four launches (the ones behind convergence return at once), the product S x of the
@@ -965,8 +1078,15 @@ template <typename T> struct Solver final : SolverBase {
         const double tol2 = pcg_rel_tol * pcg_rel_tol;
         for (int k = 0; k < pcg_max_iter; k++) {
             launch_pcg_matvec<false>(k, tol2);
-            hipLaunchKernelGGL((k_pcg_update<T>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, d_pcg_r.p,
-                               pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gq, d_pcg.p);
+            if (forest_on()) {
+                hipLaunchKernelGGL((k_pcg_update<T, true>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p,
+                                   d_pcg_r.p, pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p,
+                                   (const unsigned char *)fo.in_tree.p);
+                hipLaunchKernelGGL((k_pcg_forest_apply<T, false>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_r.p, d_pcg_z.p,
+                                   pcg_part_rz() + (size_t)((k + 1) % 3) * pcg_gz() + pcg_gc, (const ba_pcg_dev *)d_pcg.p);
+            } else
+                hipLaunchKernelGGL((k_pcg_update<T>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, d_pcg_r.p,
+                                   pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p, (const unsigned char *)nullptr);
         }
         launch_pcg_matvec<true>(pcg_max_iter, tol2);
         // (a trial ba_minimize enqueued behind the row that ended the run is not counted: lm->stop is already set when it runs)
@@ -1010,7 +1130,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs) + prior_bytes() + relpose_bytes();
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1450,6 +1570,9 @@ template <typename T> struct Solver final : SolverBase {
                 (rc = nrec.alloc((size_t)BA_RP_REC * n))) { (void)hipGetLastError(); return rc; }
             HIPCHK(hipMemset(nrec.p, 0, sizeof(T) * nrec.n));
         }
+        std::vector<int> new_pairs(pairs, pairs + 2 * (size_t)n);
+        Forest nf; // (ba_solver_set_preconditioner in front of this call: the forest of the new list)
+        if (iterative() && (rc = build_forest(new_pairs, precond_kind, precond_max_tree, nf))) return rc;
         if (gr_new != gR) {
             if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gP + 2 * (size_t)gr_new)) || (rc = npr.alloc(2 * (size_t)gr_new))) { (void)hipGetLastError(); return rc; }
             HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
@@ -1463,6 +1586,8 @@ template <typename T> struct Solver final : SolverBase {
         BA_SWAP(d_rp_Lr, nLr); BA_SWAP(d_rp_Lt, nLt); BA_SWAP(d_rp_rec, nrec);
 #undef BA_SWAP
         n_rp = n;
+        fo.swap(nf);
+        h_rp_pair.swap(new_pairs);
         return model_changed(); // (the old buffers leave with the locals)
     }
     // {sum |e_r|^2, sum |e_t|^2} of the last linearisation's partials, in index order
@@ -2306,6 +2431,11 @@ int ba_solver_set_relative_poses(ba_solver *s, int n, const int *cam_pairs, cons
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_relposes(n, cam_pairs, R0, t0, sqrt_info_rot, sqrt_info_trans);
 }
 int ba_solver_relative_pose_energy(ba_solver *s, double *out2) { return !(s && out2) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->relpose_energy(out2); }
+int ba_solver_set_preconditioner(ba_solver *s, int kind, int max_tree) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_precond(kind, max_tree); }
+int ba_solver_preconditioner_info(ba_solver *s, long long *out6, int *fallback_trees)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->precond_info(out6, fallback_trees);
+}
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

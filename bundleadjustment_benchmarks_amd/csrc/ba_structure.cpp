@@ -162,3 +162,56 @@ extern "C" int ba_shard_plan(const ba_problem *p, int shard_rank, int shard_worl
     out8[7] = s.was_sorted ? 1 : 0;
     return BA_OK;
 }
+
+// The spanning forest of the constraint graph behind BA_PRECOND_CONSTRAINT_FOREST (ba_mi355x.h states the rule; the solver builds its
+// device lists from these four arrays, tests/forest_checks.py restates it).
+extern "C" int ba_relpose_forest_plan(int N, int n, const int *cam_pairs, int max_tree, int *parent, int *via, int *order, unsigned char *kept)
+{
+    if (N < 0 || n < 0 || max_tree < 1 || (N > 0 && (!parent || !via || !order)) || (n > 0 && (!cam_pairs || !kept))) return BA_ERR_ARG;
+    for (int q = 0; q < n; q++) {
+        const int a = cam_pairs[2 * q], b = cam_pairs[2 * q + 1];
+        if (a < 0 || b < 0 || a >= N || b >= N || a == b) return BA_ERR_ARG;
+    }
+    std::vector<int> uf((size_t)N), size((size_t)N, 1), deg((size_t)N + 1, 0);
+    std::iota(uf.begin(), uf.end(), 0);
+    auto find = [&](int x) {
+        while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; }
+        return x;
+    };
+    for (int q = 0; q < n; q++) {
+        const int ra = find(cam_pairs[2 * q]), rb = find(cam_pairs[2 * q + 1]);
+        kept[q] = ra != rb && size[ra] + size[rb] <= max_tree;
+        if (!kept[q]) continue;
+        const int lo = std::min(ra, rb), hi = std::max(ra, rb); // (the representative is the component's lowest camera: its root)
+        uf[hi] = lo;
+        size[lo] += size[hi];
+        deg[cam_pairs[2 * q] + 1]++; deg[cam_pairs[2 * q + 1] + 1]++;
+    }
+    // adjacency of the kept edges, list order per camera
+    for (int a = 0; a < N; a++) deg[a + 1] += deg[a];
+    std::vector<int> adj((size_t)deg[N]), fill(deg.begin(), deg.end() - 1);
+    for (int q = 0; q < n; q++)
+        if (kept[q]) { adj[fill[cam_pairs[2 * q]]++] = q; adj[fill[cam_pairs[2 * q + 1]]++] = q; }
+    for (int a = 0; a < N; a++) { parent[a] = -1; via[a] = -1; }
+    std::vector<int> bfs;
+    std::vector<unsigned char> seen((size_t)N, 0);
+    int pos = 0;
+    for (int root = 0; root < N; root++) { // ascending root: a camera not seen yet is the lowest of its component
+        if (seen[root] || deg[root] == deg[root + 1]) continue;
+        bfs.assign(1, root);
+        seen[root] = 1;
+        for (size_t h = 0; h < bfs.size(); h++) {
+            const int c = bfs[h];
+            for (int k = deg[c]; k < deg[c + 1]; k++) {
+                const int q = adj[k], o = cam_pairs[2 * q] == c ? cam_pairs[2 * q + 1] : cam_pairs[2 * q];
+                if (seen[o]) continue;
+                seen[o] = 1; parent[o] = c; via[o] = q;
+                bfs.push_back(o);
+            }
+        }
+        for (size_t h = bfs.size(); h-- > 0;) order[pos++] = bfs[h];
+    }
+    for (int a = 0; a < N; a++)
+        if (!seen[a]) order[pos++] = a;
+    return BA_OK;
+}

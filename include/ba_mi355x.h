@@ -437,6 +437,33 @@ int ba_solver_set_relative_poses(ba_solver *s, int n, const int *cam_pairs /* 2n
  * linearisation, or a model set since the last one. */
 int ba_solver_relative_pose_energy(ba_solver *s, double *out2);
 
+/* ---- BA_ITERSCHUR's preconditioner ----------------------------------------------------------------------
+ * BA_PRECOND_BLOCK_JACOBI: M = blockdiag(B_a), B_a = V_a + lambda I - the self entries (the constraints' H_aa / H_bb are in V_a).
+ * BA_PRECOND_CONSTRAINT_FOREST: M = blockdiag(B_a) + the cross blocks H_ab (6 x 6, pose corner) of a spanning forest of the
+ * constraint graph, both triangles.  The forest: the constraints in list order through a union-find, one kept when it joins two
+ * components and the merged one has at most max_tree cameras (the others keep their diagonal blocks in B_a only); a tree's root is
+ * its lowest camera, its nodes in breadth-first order from the root (neighbours in list order), eliminated in the reverse of that
+ * order.  On a forest the block LDL^T has no fill: factored once per trial (fp64 for both scalar types), applied by two sweeps per
+ * PCG iteration, one wavefront per tree.  A tree with a pivot block that is not positive definite in working precision uses the
+ * block-Jacobi inverses of its cameras for that solve. */
+typedef enum { BA_PRECOND_BLOCK_JACOBI = 0, BA_PRECOND_CONSTRAINT_FOREST = 1 } ba_precond_kind;
+/* The default max_tree: the largest tree measured (profiles/r12_forest_measure.txt).  On an odometry chain the whole chain in one tree
+ * gave the fewest ms per trial at 257 and at 1024 cameras; a tree's factor and sweeps are sequential and grow linearly with its cameras. */
+#define BA_PCG_MAX_TREE_DEFAULT 1024
+/* BA_ITERSCHUR only.  max_tree: cameras per tree at most (>= 1; 0 = BA_PCG_MAX_TREE_DEFAULT).  Takes effect at the next
+ * try_step / ba_minimize; drops the captured trial graph like ba_solver_set_pcg.  A new solver uses BA_PRECOND_BLOCK_JACOBI; a forest
+ * without a kept constraint (no constraints, max_tree = 1) runs the block-Jacobi launches and returns their bits.
+ * ba_solver_set_relative_poses behind this call rebuilds the forest.  BA_ERR_ARG, solver unchanged: another solver kind, an unknown
+ * kind, max_tree < 0. */
+int ba_solver_set_preconditioner(ba_solver *s, int kind, int max_tree);
+/* out6 = {kind, max_tree in force, trees with >= 2 cameras, kept constraints, dropped constraints, cameras of the largest tree};
+ * *fallback_trees (may be NULL): trees of the last solve that fell back to block Jacobi.  BA_ERR_ARG for another solver kind. */
+int ba_solver_preconditioner_info(ba_solver *s, long long *out6, int *fallback_trees);
+/* Host only (no GPU), the forest rule above on a bare pair list (a pair may occur more than once): parent[N] (-1: root or lone
+ * camera), via[N] (constraint index of the edge to the parent, -1), order[N] (elimination order, tree after tree by ascending root,
+ * lone cameras last by index), kept[n] (0/1).  BA_ERR_ARG: a == b, an index out of range, max_tree < 1, N < 0, n < 0, a NULL array. */
+int ba_relpose_forest_plan(int N, int n, const int *cam_pairs, int max_tree, int *parent, int *via, int *order, unsigned char *kept);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);

@@ -25,8 +25,9 @@ FIX_T, FIX_OMEGA, FIX_POSE, FIX_INTRINSICS, FIX_CAMERA = 0x007, 0x038, 0x03F, 0x
 # ba_solver_set_loss: rho(s) of the weighted squared reprojection error s (include/ba_mi355x.h); a new solver is (LOSS_REFERENCE, 0.5)
 LOSS_REFERENCE, LOSS_TRIVIAL, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2, 3
 
-# ba_solver_set_preconditioner (ITERSCHUR): block Jacobi, or block Jacobi + the cross blocks of a spanning forest of the constraints
-PRECOND_BLOCK_JACOBI, PRECOND_CONSTRAINT_FOREST = 0, 1
+# ba_solver_set_preconditioner (ITERSCHUR): block Jacobi, or block Jacobi + the cross blocks of a spanning forest of the constraints,
+# or + the blocks S_ab of a maximum-weight spanning forest of the co-visibility graph (Problem.covisibility)
+PRECOND_BLOCK_JACOBI, PRECOND_CONSTRAINT_FOREST, PRECOND_VISIBILITY_FOREST = 0, 1, 3  # (2 is no kind: refused as before)
 
 (GET_RESIDUALS, GET_JC, GET_JP, GET_GRAD, GET_S, GET_RHS, GET_DX, GET_CAMS, GET_POINTS, GET_CAMS_TEST,
  GET_POINTS_TEST) = range(11)
@@ -44,7 +45,7 @@ EXPORTS = [
     "ba_solver_set_loss", "ba_solver_set_obs_weights",
     "ba_solver_set_point_priors", "ba_solver_set_centre_priors", "ba_solver_set_intrinsics_priors", "ba_solver_prior_energy",
     "ba_solver_set_relative_poses", "ba_solver_relative_pose_energy",
-    "ba_solver_set_preconditioner", "ba_solver_preconditioner_info", "ba_relpose_forest_plan",
+    "ba_solver_set_preconditioner", "ba_solver_preconditioner_info", "ba_relpose_forest_plan", "ba_problem_covisibility",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -150,6 +151,7 @@ def lib():
         L.ba_solver_set_preconditioner.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ba_solver_preconditioner_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_relpose_forest_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.ba_problem_covisibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -227,6 +229,16 @@ class Problem:
         _chk(lib().ba_shard_plan(self._h, rank, world, out), "ba_shard_plan")
         keys = ("p0", "p1", "o0", "o1", "entries", "chunks", "pairs", "was_sorted")
         return dict(zip(keys, [int(v) for v in out]))
+
+    def covisibility(self, track_max=0):
+        """ba_problem_covisibility (host only): (pairs [n, 2] with a < b, weight [n]) -- the camera pairs that share points and how many,
+        ordered by (weight descending, a, b).  A point seen by more than track_max cameras (0: the library's default) counts only for
+        the pairs adjacent in ascending camera index."""
+        n = C.c_longlong(0)
+        _chk(lib().ba_problem_covisibility(self._h, int(track_max), C.byref(n), None, None), "ba_problem_covisibility")
+        pairs, weight = np.zeros((n.value, 2), np.int32), np.zeros(n.value, np.int32)
+        _chk(lib().ba_problem_covisibility(self._h, int(track_max), C.byref(n), _p(pairs), _p(weight)), "ba_problem_covisibility")
+        return pairs, weight
 
     @classmethod
     def load_cache(cls, path):
@@ -348,8 +360,8 @@ class Solver:
         _chk(lib().ba_solver_set_pcg(self._h, int(max_iter), float(rel_tol)), "ba_solver_set_pcg")
 
     def set_preconditioner(self, kind, max_tree=0):
-        """ITERSCHUR: PRECOND_BLOCK_JACOBI (a new solver's) or PRECOND_CONSTRAINT_FOREST with at most max_tree cameras per tree (0: the
-        library's default)."""
+        """ITERSCHUR: PRECOND_BLOCK_JACOBI (a new solver's), PRECOND_CONSTRAINT_FOREST or PRECOND_VISIBILITY_FOREST with at most max_tree
+        cameras per tree (0: the library's default for that kind)."""
         _chk(lib().ba_solver_set_preconditioner(self._h, int(kind), int(max_tree)), "ba_solver_set_preconditioner")
 
     def preconditioner_info(self):

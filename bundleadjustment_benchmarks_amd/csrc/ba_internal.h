@@ -61,6 +61,10 @@ struct ba_structure {
 // npairs, E and nchunks stay 0 -- and none of their limits; the camera-sorted view (step 5) is built as always.
 int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *out, bool pairs = true);
 
+// The co-visibility list of ba_problem_covisibility (ba_mi355x.h states the rule) from point-sorted observations: pt_ptr[M + 1] into
+// obs_cam.  pairs: 2n (a < b), weight: n, ordered by (weight descending, a, b).
+int ba_covisibility(int N, int M, const int *pt_ptr, const int *obs_cam, int track_max, std::vector<int> &pairs, std::vector<int> &weight);
+
 // RCCL transport (ba_comm.cpp); comm is an ncclComm_t
 int ba_rccl_init(void **comm_out, const void *id128, int rank, int world);
 void ba_rccl_destroy(void *comm);

@@ -25,7 +25,7 @@
 // BA_PRECOND_CONSTRAINT_FOREST (ba_pcg_forest.hip.h): the cameras of the forest's trees (in_tree) get their z from k_pcg_forest_apply,
 // launched behind k_pcg_prec_inv and behind every k_pcg_update, which leave those cameras' z and r'z alone (FOREST instantiations).  The
 // trees' partials of r'z follow the gc per-camera ones, so the list of r'z has gz = gc + trees entries per slot (gz = gc without a
-// forest) while |r|^2 keeps gc.
+// forest) while |r|^2 keeps gc.  BA_PRECOND_VISIBILITY_FOREST is the same with one partial per 256 trees (k_pcg_forest_rz).
 #ifndef BA_PCG_HIP_H
 #define BA_PCG_HIP_H
 

@@ -926,49 +926,87 @@ template <typename T> struct Solver final : SolverBase {
     int pcg_max_iter = BA_PCG_MAX_ITER_DEFAULT;
     double pcg_rel_tol = BA_PCG_REL_TOL_DEFAULT;
     // (with a forest the list of r'z is longer by one partial per tree and the four lists live in the forest's own buffer)
-    int pcg_gz() const { return pcg_gc + (forest_on() ? fo.ntrees : 0); }
+    int pcg_gz() const { return pcg_gc + (forest_on() ? fo.nparts() : 0); }
     double *pcg_part_rz() const { return forest_on() ? fo.part.p : d_pcg_part.p; }
     double *pcg_part_rr() const { return pcg_part_rz() + (size_t)3 * pcg_gz(); }
     double *pcg_part_py() const { return pcg_part_rr() + (size_t)3 * pcg_gc; }
     double *pcg_part_res() const { return pcg_part_py() + pcg_gq; }
 
-    // ---- BA_PRECOND_CONSTRAINT_FOREST (ba_pcg_forest.hip.h) -------------------------------------------------------
+    // ---- BA_PRECOND_CONSTRAINT_FOREST / BA_PRECOND_VISIBILITY_FOREST (ba_pcg_forest.hip.h; DESIGN.md sections 15, 16) --------------------
     // The lists of ba_relpose_forest_plan in elimination order, tree after tree, built by set_precond / set_relposes.  Without a kept
-    // constraint there is no buffer and not one launch or argument differs from block Jacobi.
+    // constraint there is no buffer and not one launch or argument differs from block Jacobi.  The visibility forest plans the list
+    // L = the constraints, then the co-visibility pairs, has cross blocks of width 9 and the record pairs of every kept edge.
     struct Forest {
-        DevBuf<int> tree_ptr, node_cam, node_par, node_rec, bad;
+        DevBuf<int> tree_ptr, node_cam, node_par, node_rec, bad, edge_ptr, edge_oo;
         DevBuf<unsigned char> in_tree;
         DevBuf<T> fac, u;
-        DevBuf<double> work, part;
-        int ntrees = 0, nodes = 0, kept = 0, dropped = 0, largest = 0;
+        DevBuf<double> work, part, xc, tpart;
+        int ntrees = 0, nodes = 0, kept = 0, dropped = 0, largest = 0, width = 6;
         void swap(Forest &o)
         {
 #define BA_SWAP(A) std::swap(A.p, o.A.p); std::swap(A.n, o.A.n)
             BA_SWAP(tree_ptr); BA_SWAP(node_cam); BA_SWAP(node_par); BA_SWAP(node_rec); BA_SWAP(bad); BA_SWAP(in_tree); BA_SWAP(fac); BA_SWAP(u);
-            BA_SWAP(work); BA_SWAP(part);
+            BA_SWAP(work); BA_SWAP(part); BA_SWAP(edge_ptr); BA_SWAP(edge_oo); BA_SWAP(xc); BA_SWAP(tpart);
 #undef BA_SWAP
+            std::swap(width, o.width);
             std::swap(ntrees, o.ntrees); std::swap(nodes, o.nodes); std::swap(kept, o.kept); std::swap(dropped, o.dropped); std::swap(largest, o.largest);
         }
+        // partials of r'z behind the per-camera ones: one per tree, width 9 one per 256 trees (k_pcg_forest_rz)
+        int nparts() const { return width == 9 ? (ntrees + 255) / 256 : ntrees; }
         size_t bytes() const
         {
             return bytes_of(tree_ptr) + bytes_of(node_cam) + bytes_of(node_par) + bytes_of(node_rec) + bytes_of(bad) + bytes_of(in_tree) + bytes_of(fac) +
-                   bytes_of(u) + bytes_of(work) + bytes_of(part);
+                   bytes_of(u) + bytes_of(work) + bytes_of(part) + bytes_of(edge_ptr) + bytes_of(edge_oo) + bytes_of(xc) + bytes_of(tpart);
         }
     } fo;
     int precond_kind = BA_PRECOND_BLOCK_JACOBI, precond_max_tree = BA_PCG_MAX_TREE_DEFAULT;
     std::vector<int> h_rp_pair; // the constraint list as set (host copy for the forest)
-    bool forest_on() const { return precond_kind == BA_PRECOND_CONSTRAINT_FOREST && fo.ntrees > 0; }
+    bool forest_on() const { return precond_kind != BA_PRECOND_BLOCK_JACOBI && fo.ntrees > 0; }
     ba_forest_dev<T> forest_dev() const
     {
-        return ba_forest_dev<T>{fo.tree_ptr.p, fo.node_cam.p, fo.node_par.p, fo.node_rec.p, fo.fac.p, fo.work.p, fo.u.p, fo.bad.p};
+        return ba_forest_dev<T>{fo.tree_ptr.p, fo.node_cam.p, fo.node_par.p, fo.node_rec.p, fo.fac.p, fo.work.p, fo.u.p, fo.bad.p,
+                                fo.edge_ptr.p, fo.edge_oo.p, fo.xc.p};
+    }
+    // the forest's launches by the cross blocks' width
+    void launch_forest_edges()
+    {
+        hipLaunchKernelGGL((k_pcg_forest_edges<T>), dim3(fo.nodes), dim3(256), 0, st, forest_dev(), (const T *)d_rec.p, (const T *)d_rp_rec.p);
+    }
+    void launch_forest_factor()
+    {
+        if (fo.width == 9)
+            hipLaunchKernelGGL((k_pcg_forest_factor<T, 9>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+        else
+            hipLaunchKernelGGL((k_pcg_forest_factor<T>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+    }
+    template <bool START> void launch_forest_apply(double *part)
+    {
+        if (fo.width == 9) {
+            hipLaunchKernelGGL((k_pcg_forest_apply<T, START, 9>), dim3(fo.ntrees), dim3(64), sizeof(T) * 9 * (size_t)std::min(fo.largest, BA_FOREST_LDS), st,
+                               forest_dev(), (const T *)d_pcg_r.p, d_pcg_z.p, fo.tpart.p, (const ba_pcg_dev *)d_pcg.p);
+            hipLaunchKernelGGL((k_pcg_forest_rz<START>), dim3(fo.nparts()), dim3(256), 0, st, (const double *)fo.tpart.p, fo.ntrees, part,
+                               (const ba_pcg_dev *)d_pcg.p);
+        } else
+            hipLaunchKernelGGL((k_pcg_forest_apply<T, START>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_r.p, d_pcg_z.p, part,
+                               (const ba_pcg_dev *)d_pcg.p);
     }
     // the forest of `pairs` under (kind, max_tree) into `out`; everything that can fail, nothing of the solver touched
-    int build_forest(const std::vector<int> &pairs, int kind, int max_tree, Forest &out) const
+    int build_forest(const std::vector<int> &rp_pairs, int kind, int max_tree, Forest &out) const
     {
+        const bool vis = kind == BA_PRECOND_VISIBILITY_FOREST;
+        std::vector<int> pairs(rp_pairs); // L
+        if (vis) {
+            std::vector<int> cp, cw;
+            const int rc = ba_covisibility(N, Ml, sx.pt_ptr.data(), sx.obs_cam.data(), 0, cp, cw);
+            if (rc) return rc;
+            if (pairs.size() / 2 + cp.size() / 2 > (size_t)0x7fffffff) return BA_ERR_NOMEM;
+            pairs.insert(pairs.end(), cp.begin(), cp.end());
+            out.width = 9;
+        }
         const int n = (int)(pairs.size() / 2);
         out.dropped = n;
         out.largest = N > 0 ? 1 : 0;
-        if (kind != BA_PRECOND_CONSTRAINT_FOREST || n == 0 || max_tree < 2) return BA_OK;
+        if (kind == BA_PRECOND_BLOCK_JACOBI || n == 0 || max_tree < 2) return BA_OK;
         std::vector<int> parent((size_t)N), via((size_t)N), order((size_t)N);
         std::vector<unsigned char> kept((size_t)n);
         int rc = ba_relpose_forest_plan(N, n, pairs.data(), max_tree, parent.data(), via.data(), order.data(), kept.data());
@@ -985,7 +1023,8 @@ template <typename T> struct Solver final : SolverBase {
             const int c = order[k];
             node_cam.push_back(c);
             node_par.push_back(parent[c] >= 0 ? pos[parent[c]] : -1);
-            node_rec.push_back(parent[c] >= 0 ? 2 * via[c] + (pairs[2 * (size_t)via[c]] == c ? 0 : 1) : -1);
+            // (a kept co-visibility edge has no constraint on its pair: that one came first in L and would have been kept instead)
+            node_rec.push_back(parent[c] >= 0 && 2 * (size_t)via[c] < rp_pairs.size() ? 2 * via[c] + (pairs[2 * (size_t)via[c]] == c ? 0 : 1) : -1);
             if (parent[c] < 0) { // the root ends its tree
                 out.largest = std::max(out.largest, k + 1 - tree_ptr.back());
                 tree_ptr.push_back(k + 1);
@@ -993,9 +1032,44 @@ template <typename T> struct Solver final : SolverBase {
         }
         out.ntrees = (int)tree_ptr.size() - 1;
         out.nodes = (int)node_cam.size();
+        if (vis) { // per node the record pairs (o of the node, o' of its parent) of their common points: ascending point, then observation order
+            std::vector<int> cptr((size_t)N + 1, 0), edge_ptr(1, 0), edge_oo;
+            for (int i = 0; i < Kl; i++) cptr[(size_t)sx.obs_cam[i] + 1]++;
+            for (int a = 0; a < N; a++) cptr[a + 1] += cptr[a];
+            const std::vector<int> &co = sx.cam_obs, &op = sx.obs_pt; // (a camera's observations ascend, and with them their points)
+            for (int k = 0; k < out.nodes; k++) {
+                if (node_par[k] >= 0) {
+                    const int a = node_cam[k], b = node_cam[node_par[k]];
+                    int ia = cptr[a], ib = cptr[b];
+                    const int ea = cptr[a + 1], eb = cptr[b + 1];
+                    while (ia < ea && ib < eb) {
+                        const int pa = op[co[ia]], pb = op[co[ib]];
+                        if (pa < pb) ia++;
+                        else if (pb < pa) ib++;
+                        else {
+                            int ra = ia, rb = ib;
+                            while (ra < ea && op[co[ra]] == pa) ra++;
+                            while (rb < eb && op[co[rb]] == pa) rb++;
+                            for (int x = ia; x < ra; x++)
+                                for (int y = ib; y < rb; y++) { edge_oo.push_back(co[x]); edge_oo.push_back(co[y]); }
+                            ia = ra; ib = rb;
+                        }
+                    }
+                    if (edge_oo.size() / 2 > (size_t)0x3fffffff) return BA_ERR_NOMEM;
+                }
+                edge_ptr.push_back((int)(edge_oo.size() / 2));
+            }
+            if ((rc = out.edge_ptr.upload(edge_ptr)) || (rc = out.edge_oo.upload(edge_oo)) || (rc = out.xc.alloc((size_t)out.nodes * 81)) ||
+                (rc = out.tpart.alloc((size_t)out.ntrees))) {
+                (void)hipGetLastError();
+                return rc;
+            }
+            HIPCHK(hipMemset(out.xc.p, 0, sizeof(double) * out.xc.n));
+            HIPCHK(hipMemset(out.tpart.p, 0, sizeof(double) * out.tpart.n));
+        }
         if ((rc = out.tree_ptr.upload(tree_ptr)) || (rc = out.node_cam.upload(node_cam)) || (rc = out.node_par.upload(node_par)) ||
             (rc = out.node_rec.upload(node_rec)) || (rc = out.in_tree.upload(in_tree)) || (rc = out.bad.alloc((size_t)out.ntrees)) ||
-            (rc = out.fac.alloc((size_t)out.nodes * BA_FOREST_FAC)) || (rc = out.work.alloc((size_t)out.nodes * 81)) ||
+            (rc = out.fac.alloc((size_t)out.nodes * BA_FOREST_FAC(out.width))) || (rc = out.work.alloc((size_t)out.nodes * 81)) ||
             (rc = out.u.alloc(out.largest > BA_FOREST_LDS ? (size_t)out.nodes * 9 : 0)) ||
             (rc = out.part.alloc((size_t)3 * (pcg_gc + out.ntrees) + (size_t)3 * pcg_gc + 2 * (size_t)pcg_gq))) { (void)hipGetLastError(); return rc; }
         HIPCHK(hipMemset(out.bad.p, 0, sizeof(int) * out.bad.n));
@@ -1004,8 +1078,9 @@ template <typename T> struct Solver final : SolverBase {
     }
     int set_precond(int kind, int max_tree) override
     {
-        if (!iterative() || (kind != BA_PRECOND_BLOCK_JACOBI && kind != BA_PRECOND_CONSTRAINT_FOREST) || max_tree < 0) return BA_ERR_ARG;
-        if (max_tree == 0) max_tree = BA_PCG_MAX_TREE_DEFAULT;
+        if (!iterative() || (kind != BA_PRECOND_BLOCK_JACOBI && kind != BA_PRECOND_CONSTRAINT_FOREST && kind != BA_PRECOND_VISIBILITY_FOREST) || max_tree < 0)
+            return BA_ERR_ARG;
+        if (max_tree == 0) max_tree = kind == BA_PRECOND_VISIBILITY_FOREST ? BA_PCG_VIS_MAX_TREE_DEFAULT : BA_PCG_MAX_TREE_DEFAULT;
         Forest nf;
         int rc;
         if ((rc = build_forest(h_rp_pair, kind, max_tree, nf))) return rc;
@@ -1036,19 +1111,23 @@ template <typename T> struct Solver final : SolverBase {
 
     // segment A behind k_elim_chol: block-Jacobi preconditioner, reduced rhs, g_c for the retraction's rho terms, x_0 = 0 and the
     // recurrence's start (p_{-1} = 0, z_0, slot-0 partials, |rhs|^2)
-    void launch_pcg_prep()
+    void launch_pcg_blocks()
     {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_prec_chunks<T>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p, d_obs_pt.p,
                                d_rec.p, d_tvec.p, Ml, d_dslab.p);
         hipLaunchKernelGGL((k_pcg_prec_reduce<T>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
                            d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, d_pcg_M.p, d_pcg_b.p, d_gcg.p);
+    }
+    void launch_pcg_prep()
+    {
+        launch_pcg_blocks();
         if (forest_on()) { // the factor reads B_a in front of its inversion in place; z_0 and r_0'z_0 of the trees behind it
-            hipLaunchKernelGGL((k_pcg_forest_factor<T>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+            if (fo.width == 9) launch_forest_edges(); // (behind the elimination's and the constraints' records)
+            launch_forest_factor();
             hipLaunchKernelGGL((k_pcg_prec_inv<T, true>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
                                pcg_part_rz(), pcg_part_rr(), (const unsigned char *)fo.in_tree.p);
-            hipLaunchKernelGGL((k_pcg_forest_apply<T, true>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_r.p, d_pcg_z.p,
-                               pcg_part_rz() + pcg_gc, (const ba_pcg_dev *)d_pcg.p);
+            launch_forest_apply<true>(pcg_part_rz() + pcg_gc);
         } else
             hipLaunchKernelGGL((k_pcg_prec_inv<T>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
                                pcg_part_rz(), pcg_part_rr(), (const unsigned char *)nullptr);
@@ -1082,8 +1161,7 @@ template <typename T> struct Solver final : SolverBase {
                 hipLaunchKernelGGL((k_pcg_update<T, true>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p,
                                    d_pcg_r.p, pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p,
                                    (const unsigned char *)fo.in_tree.p);
-                hipLaunchKernelGGL((k_pcg_forest_apply<T, false>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_r.p, d_pcg_z.p,
-                                   pcg_part_rz() + (size_t)((k + 1) % 3) * pcg_gz() + pcg_gc, (const ba_pcg_dev *)d_pcg.p);
+                launch_forest_apply<false>(pcg_part_rz() + (size_t)((k + 1) % 3) * pcg_gz() + pcg_gc);
             } else
                 hipLaunchKernelGGL((k_pcg_update<T>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, d_pcg_r.p,
                                    pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p, (const unsigned char *)nullptr);
@@ -2217,6 +2295,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         if (reps < 1 || !ms) return BA_ERR_ARG;
         if (iterative() && (phase == 3 || phase == 6 || phase == 7)) return BA_ERR_ARG; // (no S)
+        if ((phase == 9 || phase == 10) && !(iterative() && forest_on() && (phase == 10 || fo.width == 9))) return BA_ERR_ARG;
         double acc_ms = 0;
         int rcl = set_lambda((T)lambda_d);
         if (rcl) return rcl;
@@ -2240,6 +2319,16 @@ template <typename T> struct Solver final : SolverBase {
                 launch_grad(nullptr, nullptr, !fuse);
                 if (priors()) launch_prior(true, 0, nullptr);
                 if (relposes()) launch_relpose(true, 0, nullptr);
+                break;
+            case 9: launch_forest_edges(); break;
+            case 10: // the forest's factor alone: events around it, per rep (it needs B_a, which the trial inverts in place)
+                launch_pcg_blocks();
+                if (fo.width == 9) launch_forest_edges();
+                HIPCHK(hipEventRecord(ev[EV_T2], st));
+                launch_forest_factor();
+                HIPCHK(hipEventRecord(ev[EV_T3], st));
+                HIPCHK(hipStreamSynchronize(st));
+                acc_ms += ev_ms(EV_T2, EV_T3);
                 break;
             case 6: // dense factorisation only (k_ldlt_panel + k_ldlt_step / k_ldlt_update; QRKIT: the Householder QR + solve): events around it, per rep
             case 7: // backward sweep only (k_ldlt_backflow; QRKIT: nothing, the solve is part of 6)
@@ -2268,7 +2357,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipEventRecord(ev[EV_T1], st));
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
-        *ms = ((phase == 6 || phase == 7) ? acc_ms : ev_ms(EV_T0, EV_T1)) / reps;
+        *ms = ((phase == 6 || phase == 7 || phase == 10) ? acc_ms : ev_ms(EV_T0, EV_T1)) / reps;
         have_step = false;
         return BA_OK;
     }

@@ -9,7 +9,9 @@
 #include "ba_internal.h"
 
 #include <algorithm>
+#include <new>
 #include <numeric>
+#include <utility>
 
 int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *s, bool pairs)
 {
@@ -213,5 +215,91 @@ extern "C" int ba_relpose_forest_plan(int N, int n, const int *cam_pairs, int ma
     }
     for (int a = 0; a < N; a++)
         if (!seen[a]) order[pos++] = a;
+    return BA_OK;
+}
+
+// The co-visibility graph behind BA_PRECOND_VISIBILITY_FOREST (ba_mi355x.h states the rule, tests/visibility_checks.py restates it).
+// Counts: dense N x N up to 2048 cameras; beyond that packed keys a N + b, sorted and run-length counted whenever 16 M of them have
+// gathered, the runs merged into the sorted list so far -- memory follows the number of distinct pairs, not the number of points.
+int ba_covisibility(int N, int M, const int *pt_ptr, const int *obs_cam, int track_max, std::vector<int> &pairs, std::vector<int> &weight)
+{
+    if (track_max == 0) track_max = BA_VIS_TRACK_MAX_DEFAULT;
+    if (N < 0 || M < 0 || track_max < 0 || (M > 0 && (!pt_ptr || !obs_cam))) return BA_ERR_ARG;
+    pairs.clear();
+    weight.clear();
+    const bool dense = N <= 2048;
+    std::vector<int> cnt(dense ? (size_t)N * N : 0, 0);
+    std::vector<long long> keys;
+    std::vector<std::pair<long long, int>> acc, run, merged; // (key, count), key ascending
+    auto flush = [&]() {
+        std::sort(keys.begin(), keys.end());
+        run.clear();
+        for (size_t i = 0; i < keys.size();) {
+            size_t j = i;
+            while (j < keys.size() && keys[j] == keys[i]) j++;
+            run.emplace_back(keys[i], (int)(j - i));
+            i = j;
+        }
+        keys.clear();
+        merged.clear();
+        merged.reserve(acc.size() + run.size());
+        size_t x = 0, y = 0;
+        while (x < acc.size() || y < run.size()) {
+            if (y == run.size() || (x < acc.size() && acc[x].first < run[y].first)) merged.push_back(acc[x++]);
+            else if (x == acc.size() || run[y].first < acc[x].first) merged.push_back(run[y++]);
+            else { merged.emplace_back(acc[x].first, acc[x].second + run[y].second); x++; y++; }
+        }
+        acc.swap(merged);
+    };
+    std::vector<int> cams;
+    for (int j = 0; j < M; j++) {
+        cams.assign(obs_cam + pt_ptr[j], obs_cam + pt_ptr[j + 1]);
+        std::sort(cams.begin(), cams.end());
+        cams.erase(std::unique(cams.begin(), cams.end()), cams.end());
+        const int t = (int)cams.size();
+        for (int i = 0; i + 1 < t; i++) {
+            const int last = t <= track_max ? t - 1 : i + 1; // (a long track: the next camera alone)
+            for (int k = i + 1; k <= last; k++) {
+                if (dense) cnt[(size_t)cams[i] * N + cams[k]]++;
+                else keys.push_back((long long)cams[i] * N + cams[k]);
+            }
+        }
+        if (keys.size() >= ((size_t)1 << 24)) flush();
+    }
+    if (dense) {
+        for (size_t q = 0; q < cnt.size(); q++)
+            if (cnt[q]) acc.emplace_back((long long)q, cnt[q]);
+    } else
+        flush();
+    std::stable_sort(acc.begin(), acc.end(), [](const std::pair<long long, int> &u, const std::pair<long long, int> &v) { return u.second > v.second; });
+    pairs.reserve(2 * acc.size());
+    weight.reserve(acc.size());
+    for (const auto &kv : acc) {
+        pairs.push_back((int)(kv.first / N));
+        pairs.push_back((int)(kv.first % N));
+        weight.push_back(kv.second);
+    }
+    return BA_OK;
+}
+
+extern "C" int ba_problem_covisibility(const ba_problem *p, int track_max, long long *n_pairs, int *pairs, int *weight)
+{
+    if (!p || !n_pairs || track_max < 0 || (pairs == nullptr) != (weight == nullptr)) return BA_ERR_ARG;
+    try {
+        std::vector<int> ptr((size_t)p->M + 1, 0), cam((size_t)p->K), hp, hw;
+        for (int i = 0; i < p->K; i++) ptr[(size_t)p->pt_idx[i] + 1]++;
+        for (int j = 0; j < p->M; j++) ptr[j + 1] += ptr[j];
+        std::vector<int> cur(ptr.begin(), ptr.end() - 1);
+        for (int i = 0; i < p->K; i++) cam[cur[p->pt_idx[i]]++] = p->cam_idx[i];
+        const int rc = ba_covisibility(p->N, p->M, ptr.data(), cam.data(), track_max, hp, hw);
+        if (rc) return rc;
+        *n_pairs = (long long)hw.size();
+        if (pairs) {
+            std::copy(hp.begin(), hp.end(), pairs);
+            std::copy(hw.begin(), hw.end(), weight);
+        }
+    } catch (const std::bad_alloc &) {
+        return BA_ERR_NOMEM;
+    }
     return BA_OK;
 }

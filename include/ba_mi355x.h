@@ -243,7 +243,9 @@ int ba_solver_timing(ba_solver *s, ba_timing *out, int reset);
  * (HIP events on that stream).  phase: 0 residual eval, 1 residual+Jacobian, 2 point elimination,
  * 3 Schur assembly, 4 Schur assembly + dense factor + solve, 5 back-substitution + retraction,
  * 6 dense factorisation only, 7 backward sweep only (6 / 7 rebuild S untimed before every repetition).
- * BA_ITERSCHUR: 4 = preconditioner + rhs + the PCG solve; 3, 6 and 7 return BA_ERR_ARG (there is no S). */
+ * BA_ITERSCHUR: 4 = preconditioner + rhs + the PCG solve; 3, 6 and 7 return BA_ERR_ARG (there is no S); with a forest
+ * preconditioner in force 9 = the edge blocks S_ab alone (BA_PRECOND_VISIBILITY_FOREST), 10 = the forest's factor alone (B_a
+ * rebuilt untimed before every repetition); BA_ERR_ARG without one. */
 int ba_solver_time_phase(ba_solver *s, int phase, int reps, double lambda, double *ms_per_launch);
 
 /* A hand-off between workgroups of one launch that times out (the fused factorisation's row flag, the one-launch back sweep's
@@ -445,24 +447,48 @@ int ba_solver_relative_pose_energy(ba_solver *s, double *out2);
  * its lowest camera, its nodes in breadth-first order from the root (neighbours in list order), eliminated in the reverse of that
  * order.  On a forest the block LDL^T has no fill: factored once per trial (fp64 for both scalar types), applied by two sweeps per
  * PCG iteration, one wavefront per tree.  A tree with a pivot block that is not positive definite in working precision uses the
- * block-Jacobi inverses of its cameras for that solve. */
-typedef enum { BA_PRECOND_BLOCK_JACOBI = 0, BA_PRECOND_CONSTRAINT_FOREST = 1 } ba_precond_kind;
+ * block-Jacobi inverses of its cameras for that solve.
+ * BA_PRECOND_VISIBILITY_FOREST (Kushal and Agarwal's visibility-based preconditioning, what Ceres calls
+ * CLUSTER_TRIDIAGONAL): M = blockdiag(B_a) + the whole off-diagonal blocks S_ab (9 x 9) of the reduced camera matrix on a spanning
+ * forest of the co-visibility graph, both triangles.  The forest is the rule above on the list L = the solver's relative-pose pairs
+ * in list order, then ba_problem_covisibility's pairs (weight descending): a greedy maximum-weight forest by shared points behind the
+ * constraints.  S_ab = - sum over the common points p, o in a at p, o' in b at p, of Z_o diag(dinv_p) Z_o'^T (+ H_ab of a constraint
+ * on that pair, pose corner) is computed once per trial from the elimination's records, S never formed, and kept in fp64.  This M is
+ * NOT guaranteed positive definite; a tree with a pivot block that is not positive definite runs that solve on the block-Jacobi
+ * inverses of its cameras and is counted (fallback_trees). */
+/* (2 is not a kind and stays refused with BA_ERR_ARG, as it was before the visibility forest existed: callers and tests that probe
+ * for an unknown kind with it keep their behaviour) */
+typedef enum { BA_PRECOND_BLOCK_JACOBI = 0, BA_PRECOND_CONSTRAINT_FOREST = 1, BA_PRECOND_VISIBILITY_FOREST = 3 } ba_precond_kind;
 /* The default max_tree: the largest tree measured (profiles/r12_forest_measure.txt).  On an odometry chain the whole chain in one tree
  * gave the fewest ms per trial at 257 and at 1024 cameras; a tree's factor and sweeps are sequential and grow linearly with its cameras. */
 #define BA_PCG_MAX_TREE_DEFAULT 1024
-/* BA_ITERSCHUR only.  max_tree: cameras per tree at most (>= 1; 0 = BA_PCG_MAX_TREE_DEFAULT).  Takes effect at the next
+/* The default max_tree of BA_PRECOND_VISIBILITY_FOREST: the setting with the fewest ms per trial at synthetic(70 000, 280 000, 1.12 M)
+ * among 4, 8, 16, 64 and 256 (profiles/r13_visibility_measure.txt: 48.3 ms at 4, 66.0 at 8, 193.4 at 256; block Jacobi 44.8).  No
+ * setting beat block Jacobi there; larger trees needed MORE iterations on that problem, whose camera pairs share one or two points. */
+#define BA_PCG_VIS_MAX_TREE_DEFAULT 4
+/* BA_ITERSCHUR only.  max_tree: cameras per tree at most (>= 1; 0 = BA_PCG_MAX_TREE_DEFAULT, BA_PCG_VIS_MAX_TREE_DEFAULT for the
+ * visibility forest).  Takes effect at the next
  * try_step / ba_minimize; drops the captured trial graph like ba_solver_set_pcg.  A new solver uses BA_PRECOND_BLOCK_JACOBI; a forest
  * without a kept constraint (no constraints, max_tree = 1) runs the block-Jacobi launches and returns their bits.
  * ba_solver_set_relative_poses behind this call rebuilds the forest.  BA_ERR_ARG, solver unchanged: another solver kind, an unknown
  * kind, max_tree < 0. */
 int ba_solver_set_preconditioner(ba_solver *s, int kind, int max_tree);
-/* out6 = {kind, max_tree in force, trees with >= 2 cameras, kept constraints, dropped constraints, cameras of the largest tree};
+/* out6 = {kind, max_tree in force, trees with >= 2 cameras, kept constraints, dropped constraints, cameras of the largest tree}
+ * (BA_PRECOND_VISIBILITY_FOREST: kept and dropped count the entries of L);
  * *fallback_trees (may be NULL): trees of the last solve that fell back to block Jacobi.  BA_ERR_ARG for another solver kind. */
 int ba_solver_preconditioner_info(ba_solver *s, long long *out6, int *fallback_trees);
 /* Host only (no GPU), the forest rule above on a bare pair list (a pair may occur more than once): parent[N] (-1: root or lone
  * camera), via[N] (constraint index of the edge to the parent, -1), order[N] (elimination order, tree after tree by ascending root,
  * lone cameras last by index), kept[n] (0/1).  BA_ERR_ARG: a == b, an index out of range, max_tree < 1, N < 0, n < 0, a NULL array. */
 int ba_relpose_forest_plan(int N, int n, const int *cam_pairs, int max_tree, int *parent, int *via, int *order, unsigned char *kept);
+/* Host only (no GPU): the co-visibility graph of a problem.  The weight of a camera pair (a < b) is the number of points that put it
+ * together: a point seen by t <= track_max distinct cameras adds 1 to each of its t (t - 1) / 2 pairs, a longer track only to the
+ * t - 1 pairs of cameras adjacent in ascending camera index (which bounds the work on long tracks); a camera that sees a point twice
+ * counts once.  track_max = 0: BA_VIS_TRACK_MAX_DEFAULT.  Constant-parameter masks play no part.  Call with pairs = NULL for the count
+ * *n_pairs, then with pairs[2 n] and weight[n]: ordered by (weight descending, a ascending, b ascending), whatever the order of the
+ * problem's observations.  BA_ERR_ARG: a NULL problem or n_pairs, track_max < 0, one of pairs / weight NULL and the other not. */
+#define BA_VIS_TRACK_MAX_DEFAULT 64
+int ba_problem_covisibility(const ba_problem *p, int track_max, long long *n_pairs, int *pairs, int *weight);
 
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);

@@ -11,8 +11,8 @@
 //                   builds the tile's inverse one pivot behind, the others do MFMA work beside them (ba_panel_body) --
 //                   and keeps W = L11^-1; the rows below then need Y = A21 W^T, a GEMM on the matrix cores.
 //   k_ldlt_step     fused step with look-ahead: panel of block column p, the previous panel's update of block column p
-//                   (diagonal block inside the panel workgroups, their rows on workgroups of their own) and the rest of
-//                   the previous panel's trailing update, in ONE launch per block column.
+//                   (diagonal block inside the panel workgroups, their rows on workgroups of their own) and this launch's
+//                   share of the trailing update (a list of jobs, ba_ldlt_schedule.h), in ONE launch per block column.
 //   k_ldlt_update   stand-alone trailing update S_ij -= (L D)_i L_j^T on the matrix cores (v_mfma_f64_16x16x4_f64 /
 //                   v_mfma_f32_16x16x4_f32) -- the one true contraction of the LM trial.
 //   k_ldlt_backflow backward sweep L^T x = z in one launch (data flow between workgroups), using the stored W (x_p = W_p^T z_p);
@@ -28,6 +28,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
+#include "ba_ldlt_schedule.h"
 #include "ba_mfma.hip.h"
 
 // 1/d to (nearly) full precision: hardware estimate + two Newton steps (the division expansion would sit on the
@@ -129,6 +132,9 @@ __device__ __forceinline__ void ba_update_quad(int ld, int p0, int row0t, int co
                                                const T *__restrict__ Wp, T (*Cl)[NB + 1], int quad);
 template <typename T, int NB>
 __device__ __attribute__((noinline)) void ba_update_quad_call(int ld, int p0, int row0t, int col0t, T *S, const T *Wp, int quad);
+template <typename T, int NB>
+__device__ __forceinline__ void ba_update_job(int ld, int pa, int npan, int row0t, int col0t, bool lower, T *__restrict__ S,
+                                              const T *__restrict__ Wa, size_t wsz, int quad);
 template <typename T, int NB>
 __device__ __forceinline__ void ba_update_macro(int nrows, int ncols, int ld, int pA, int row0, int col0, T *__restrict__ S,
                                                 const T *__restrict__ W1, const T *__restrict__ W2, T *__restrict__ As, T *__restrict__ Bs);
@@ -626,8 +632,9 @@ __global__ __launch_bounds__(256) void k_ldlt_panel(int nrows, int ncols, int ld
 
 // Fused step with look-ahead: ONE launch per block column p0 >= 64.
 //   workgroups [0, npanel)        : panel step of block column p0 (after applying the previous panel's update to it);
-//   workgroups [npanel, gridDim.x): the rest of the trailing update of block column p0 - 64 (tiles with columns >= p0 + 64).
-// The two groups touch disjoint parts of S; Wp is double-buffered (Wprev read, Wp written).  The panel's 2313-long pivot
+//   workgroups [npanel, gridDim.x): trailing update of tiles with columns >= p0 + 64 -- k_ldlt_step: one update job each, panels no
+//                                   later than p0 - 64 (ba_ldlt_schedule.h); k_ldlt_step2: block column p0 - 64 or a pair of panels.
+// The two groups touch disjoint parts of S; the Y of this panel goes to a slot of its own (Wprev read, Wp written).  The panel's 2313-long pivot
 // recurrence is the critical path of the factorisation; this hides the MFMA update behind it.
 //
 // INL = true (D <~ 3000: one workgroup per CU, the panel is the critical path): nq further workgroups in FRONT of the grid take
@@ -642,7 +649,8 @@ template <typename T> struct ba_macro_job { const T *W1, *W2; int pM, base, coun
 template <typename T, int NB, bool INL, bool MACRO>
 __device__ __forceinline__ void ba_step_body(int nrows, int ncols, int ld, int p0, int npanel, T *__restrict__ S, T *__restrict__ Wp,
                                              const T *__restrict__ Wprev, T *__restrict__ Winv, int nq, int *__restrict__ flags,
-                                             T *__restrict__ errw, int upd_mode, int n64, const ba_macro_job<T> &mj, int fault)
+                                             T *__restrict__ errw, int upd_mode, int n64, const ba_macro_job<T> &mj, int fault,
+                                             const int4 *__restrict__ jobs = nullptr, const T *__restrict__ W0 = nullptr)
 {
     __shared__ T Ad[NB][NB + 1], Wl[NB][NB + 1];
     int bid = blockIdx.x;
@@ -658,6 +666,15 @@ __device__ __forceinline__ void ba_step_body(int nrows, int ncols, int ld, int p
     if (INL) bid -= nq;
     if (bid < npanel) {
         ba_panel_body<T, NB, INL>(nrows, ncols, ld, p0, S, Wp, Winv, Wprev, bid, npanel, Ad, Wl, INL ? flags : nullptr, p0 / NB, errw, fault);
+        return;
+    }
+    if (!MACRO) {
+        // k_ldlt_step: the trailing update of this launch is a list of jobs (ba_ldlt_schedule.h), one per workgroup behind the panel
+        // workgroups: panels a ... a + n - 1 (Y in the history W0, one panel per ld x NB slot) on tile (ti, tj), block column tj
+        // > p: the tile is read once, takes the panels in ascending order and is written once (write-through, see below).
+        const int4 job = jobs[bid - npanel];
+        ba_update_job<T, NB>(ld, NB * job.z, job.w, NB * job.x, NB * job.y, job.x == job.y, S, W0 + (size_t)job.z * ((size_t)ld * NB), (size_t)ld * NB,
+                             threadIdx.x >> 6);
         return;
     }
     // Trailing update by the workgroups behind the panel workgroups.  First n64 workgroups with 64 x 64 tiles and panel p - 1 alone:
@@ -702,10 +719,12 @@ __device__ __forceinline__ void ba_step_body(int nrows, int ncols, int ld, int p
 template <typename T, int NB, bool INL>
 __global__ __launch_bounds__(256) void k_ldlt_step(int nrows, int ncols, int ld, int p0, int npanel, T *__restrict__ S,
                                                    T *__restrict__ Wp, const T *__restrict__ Wprev, T *__restrict__ Winv,
-                                                   int nq = 0, int *__restrict__ flags = nullptr, T *__restrict__ errw = nullptr, int fault = 0)
+                                                   int nq, int *__restrict__ flags, T *__restrict__ errw, int fault,
+                                                   const int4 *__restrict__ jobs /* this launch's update jobs (ti, tj, a, n) */,
+                                                   const T *__restrict__ W0 /* Y history: panel q at W0 + q ld NB */)
 {
     static_assert(INL, "the two-per-CU variant is k_ldlt_step2");
-    ba_step_body<T, NB, true, false>(nrows, ncols, ld, p0, npanel, S, Wp, Wprev, Winv, nq, flags, errw, 0, 1 << 30, ba_macro_job<T>{}, fault);
+    ba_step_body<T, NB, true, false>(nrows, ncols, ld, p0, npanel, S, Wp, Wprev, Winv, nq, flags, errw, 0, 0, ba_macro_job<T>{}, fault, jobs, W0);
 }
 
 // The two-workgroups-per-CU variant for update-bound sizes (no dynamic-LDS request): the same panel structure -- row workgroups in
@@ -787,6 +806,69 @@ __device__ __forceinline__ void ba_update_tile(int ld, int p0, int row0t, int co
                                                const T *__restrict__ Wp, T (*Cl)[NB + 1])
 {
     ba_update_quad<T, NB, TOLDS, STSC>(ld, p0, row0t, col0t, lower, S, Wp, Cl, threadIdx.x >> 6); // wave w owns quadrant w
+}
+
+// One update job of k_ldlt_step: the panels at block columns pa, pa + NB, ... (npan of them, Y of panel m at Wa + m wsz) applied to one
+// 64 x 64 tile in ascending order.  Per panel this is ba_update_quad's operand and MFMA sequence -- the same k order in chunks of
+// eight k-steps, the same negation at use -- on accumulators that stay in registers between the panels instead of passing through
+// S: every element sees the chain of MFMAs that one launch per panel gave it, bit for bit.  The operands of the next chunk (of this
+// panel or the next one) are requested ahead of the current chunk's MFMAs; the MFMA order is untouched by that.  Results leave
+// with write-through stores like every trailing tile (the next launch reads them).
+template <typename T, int NB>
+__device__ __forceinline__ void ba_update_job(int ld, int pa, int npan, int row0t, int col0t, bool lower, T *__restrict__ S,
+                                              const T *__restrict__ Wa, size_t wsz, int quad)
+{
+    const int lane = threadIdx.x & 63;
+    const int qr = 32 * (quad >> 1), qc = 32 * (quad & 1);
+    if (lower && qc > qr) return;
+    const int row0 = row0t + qr, col0 = col0t + qc;
+    const int li = lane & 15, lk = lane >> 4;
+    typename ba_acc<T>::type acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) acc[t][u][v] = S[(size_t)(col0 + 16 * t + ba_crow<T>(lk, v)) * ld + row0 + 16 * u + li];
+    constexpr int CH = 8, CPP = (NB / 4) / CH; // k-steps per chunk (as ba_update_quad's trailing tiles), chunks per panel
+    static_assert(CPP == 2, "the loop below takes two chunks per round");
+    T a0[CH][2], b0[CH][2], a1[CH][2], b1[CH][2];
+    auto request = [&](int c, T (&a)[CH][2], T (&b)[CH][2]) {
+        const int m = c / CPP, k0 = 4 * CH * (c % CPP) + lk;
+        const T *const Lp = S + (size_t)(pa + NB * m + k0) * ld + col0 + li; // A[j][k] = L[j][k] (negated at use)
+        const T *const Yp = Wa + (size_t)m * wsz + (size_t)k0 * ld + row0 + li; // B[k][i] = Y[i][k]
+#pragma unroll
+        for (int q = 0; q < CH; q++) {
+#pragma unroll
+            for (int t = 0; t < 2; t++) a[q][t] = Lp[(size_t)(4 * q) * ld + 16 * t];
+#pragma unroll
+            for (int u = 0; u < 2; u++) b[q][u] = Yp[(size_t)(4 * q) * ld + 16 * u];
+        }
+    };
+    auto apply = [&](const T (&a)[CH][2], const T (&b)[CH][2]) {
+#pragma unroll
+        for (int q = 0; q < CH; q++)
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int u = 0; u < 2; u++) acc[t][u] = ba_mfma(-a[q][t], b[q][u], acc[t][u]);
+    };
+    request(0, a0, b0);
+#pragma unroll 1
+    for (int m = 0; m < npan; m++) {
+        request(CPP * m + 1, a1, b1);
+        apply(a0, b0);
+        if (m + 1 < npan) request(CPP * m + 2, a0, b0);
+        apply(a1, b1);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+#pragma unroll
+            for (int v = 0; v < 4; v++)
+                __hip_atomic_store(&S[(size_t)(col0 + 16 * t + ba_crow<T>(lk, v)) * ld + row0 + 16 * u + li], acc[t][u][v], __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Trailing update of one 128 x 128 MACRO tile with TWO panels (block columns pA and pA + 64: K = 128), operands staged through
@@ -1211,14 +1293,56 @@ inline void ba_ldlt_backsweep(hipStream_t st, int ncols, int ld, int zrow, T *S,
     hipLaunchKernelGGL((k_ldlt_backflow<T, NB>), dim3(2 * groups), dim3(256), 0, st, ncols, ld, zrow, nblk, S, Winv, x, zh, errw, (int)BA_SWEEP_SPINS);
 }
 
+// The trailing-update schedule of the fused steps below 48 block columns (k_ldlt_step), made once per matrix size: the job lists of
+// ba_ldlt_schedule.h as (ti, tj, a, n) quadruples for the device (the caller uploads them once, ba_ldlt_plan::d_jobs) and the host's
+// index of every launch's first job.  Two environment variables, read here, choose the schedule:
+//   BA_LDLT_UPD_BUDGET=<units>  (tile, panel) units per launch beyond which nothing is added that no deadline forces; 0 = only
+//                               what the deadlines and the cap force; a value past the number of tiles (say 1000000) = the textbook
+//                               order, panel p - 1 on every trailing tile in launch p, one panel per job
+//   BA_LDLT_UPD_CAP=<depth>     most panels one job applies to its tile (1 = the textbook order as well)
+// (BA_LDLT_PAIR_MIN=<blocks>, read in ba_ldlt_factor, belongs to k_ldlt_step2: block columns left at which its pair phase ends.)
+#define BA_LDLT_UPD_BUDGET_DEFAULT 0
+#define BA_LDLT_UPD_CAP_DEFAULT 3
+struct ba_ldlt_plan {
+    std::vector<int> jobs;  // 4 ints per job: ti, tj, a, n
+    std::vector<int> first; // launch p runs jobs first[p] ... first[p + 1] - 1
+    const int *d_jobs = nullptr; // the same on the device
+    int nrows = 0, ncols = 0;
+};
+// Panels of Y = L D the factorisation keeps (Wp: that many ld x NB slots): the whole history below 48 block columns -- a deferred
+// job reads the Y of panels older than the previous one, and recomputing L D would not be bit-equal --, four beyond (k_ldlt_step2).
+inline int ba_ldlt_wp_panels(int ncols, int NB) { const int nblk = (ncols + NB - 1) / NB; return nblk >= 2 && nblk < 48 ? std::max(nblk, 4) : 4; }
+inline ba_ldlt_plan ba_ldlt_make_plan(int nrows, int ncols, int NB, long long budget, int cap, long long slope = 0)
+{
+    ba_ldlt_plan pl;
+    pl.nrows = nrows; pl.ncols = ncols;
+    const ba_ldlt_schedule s = ba_ldlt_make_schedule((nrows + NB - 1) / NB, (ncols + NB - 1) / NB, budget, cap, slope);
+    pl.first = s.first;
+    pl.jobs.reserve(4 * s.jobs.size() + 4);
+    for (const ba_ldlt_job &j : s.jobs) { pl.jobs.push_back(j.ti); pl.jobs.push_back(j.tj); pl.jobs.push_back(j.a); pl.jobs.push_back(j.n); }
+    pl.jobs.insert(pl.jobs.end(), 4, 0); // (never empty: two block columns have no trailing tile)
+    return pl;
+}
+inline ba_ldlt_plan ba_ldlt_make_plan(int nrows, int ncols, int NB)
+{
+    const char *eb = getenv("BA_LDLT_UPD_BUDGET"), *ec = getenv("BA_LDLT_UPD_CAP");
+    return ba_ldlt_make_plan(nrows, ncols, NB, eb ? atoll(eb) : BA_LDLT_UPD_BUDGET_DEFAULT, ec ? atoi(ec) : BA_LDLT_UPD_CAP_DEFAULT);
+}
+
 // Host side of the factorisation on `st`: one k_ldlt_panel launch for the first block column, then one fused k_ldlt_step per
 // block column (or panel + update launches for a single block column).  flags: nflags ints (hand-off flags of the row
-// workgroups), Wp: 2 * ld * NB (double-buffered Y = L D panel), Winv: one NB x NB inverse per block column.
+// workgroups), Wp: ba_ldlt_wp_panels() slots of ld * NB (the Y = L D panels: slot p below 48 block columns, p % 4 beyond), Winv:
+// one NB x NB inverse per block column.
+// plan (below 48 block columns): the trailing-update jobs of every fused launch, made for this nrows x ncols and uploaded ONCE by
+// the caller -- nothing here depends on the trial, so the captured launch sequence only carries pointers into it.  Launch p runs
+// its row workgroups (panel p - 1 on block column p), its panel workgroups and behind them one workgroup per job; a job may apply
+// panels as old as the schedule left them, at most BA_LDLT_UPD_CAP of them, and block column p + 1 is complete up to panel p - 1
+// when the launch ends.  Without a plan those sizes take the panel + update launches.
 // safe: panel + update launches per block column (no workgroup waits for another one of its launch) -- the retry path after a
 // hand-off time-out; fault: self-test, the row workgroups of the fused steps stay silent.
 template <typename T, int NB>
 inline void ba_ldlt_factor(hipStream_t st, int nrows, int ncols, int ld, T *S, T *Wp, T *Winv, int *flags, int nflags, T *errw = nullptr,
-                           bool safe = false, int fault = 0)
+                           bool safe = false, int fault = 0, const ba_ldlt_plan *plan = nullptr)
 {
     const int nblk = (ncols + NB - 1) / NB;
     const size_t wsz = (size_t)ld * NB;
@@ -1228,10 +1352,10 @@ inline void ba_ldlt_factor(hipStream_t st, int nrows, int ncols, int ld, T *S, T
         const int p0 = p * NB;
         const int below = nrows - (p0 + NB);
         const int npanel = below > 0 ? (below + 63) / 64 : 1;
-        T *wcur = Wp + (size_t)(k128 ? p % 4 : (p & 1)) * wsz, *wprev = Wp + (size_t)(k128 ? (p + 3) % 4 : ((p + 1) & 1)) * wsz;
         // The fused look-ahead step wins at every size (dense bench, D = 100 ... 9216): it saves a launch per block column
         // and keeps the previous panel's update off the diagonal block's path.
-        const bool fused = nblk >= 2 && !safe;
+        const bool fused = nblk >= 2 && !safe && (k128 || (plan && plan->d_jobs && plan->nrows == nrows && plan->ncols == ncols));
+        T *wcur = Wp + (size_t)(k128 ? p % 4 : fused ? p : 0) * wsz, *wprev = Wp + (size_t)(k128 ? (p + 3) % 4 : fused ? p - 1 : 0) * wsz;
         if (p == 0 || !fused) {
             hipLaunchKernelGGL((k_ldlt_panel<T, NB>), dim3(npanel), dim3(256), 0, st, nrows, ncols, ld, p0, S, fused ? wcur : Wp,
                                Winv + (size_t)p * NB * NB, flags, nflags);
@@ -1243,7 +1367,7 @@ inline void ba_ldlt_factor(hipStream_t st, int nrows, int ncols, int ld, T *S, T
         } else {
             // trailing tiles of block column p0 - 64 outside block column p0: rows p0 + 64 ti, cols p0 + 64 tj, 1 <= tj <= ti
             const int nt = (nrows - p0 + 63) / 64, ntc = (ncols - p0 + 63) / 64;
-            int nupd = 0;
+            int nupd = 0; // (k_ldlt_step2's single-panel steps: panel p - 1 on every trailing tile)
             for (int ti = 1; ti < nt; ti++) nupd += ti < ntc - 1 ? ti : ntc - 1;
             // Up to D ~ 3000 the panel is the critical path: the variant with the look-ahead update inlined into the
             // sub-panel loop (one workgroup per CU by its dynamic-LDS request, so a panel workgroup never shares its CU
@@ -1252,11 +1376,13 @@ inline void ba_ldlt_factor(hipStream_t st, int nrows, int ncols, int ld, T *S, T
             if (!k128) {
                 const int nq = below > 0 ? npanel : 0;      // workgroups that update the panel workgroups' rows (see k_ldlt_step)
                 const int np2 = below > 0 ? 2 * npanel : 1; // two panel workgroups per 64-row block (32 rows of the row GEMM each)
-                // (the first three steps of a 37-block factorisation are update-bound -- 20 us against the 14 us of the panel chain:
-                // there the workgroups may share a CU; 0.545 -> 0.540 ms at D = 2313, and slower again from step 6 on)
-                const unsigned dyn_lds = (p <= 3 && nblk >= 32) ? 0 : 8192;
-                hipLaunchKernelGGL((k_ldlt_step<T, NB, true>), dim3(nq + np2 + nupd), dim3(256), dyn_lds, st, nrows, ncols, ld, p0, np2, S, wcur,
-                                   wprev, Winv + (size_t)p * NB * NB, nq, flags, errw, fault);
+                // (one workgroup per CU in every launch, by the dynamic-LDS request.  While launch p applied panel p - 1 to every trailing
+                // tile at once, the first three launches of a 37-block factorisation were update-bound and went without it, 0.545 ->
+                // 0.540 ms at D = 2313; under the levelled schedule no launch is, and the exception measures +-0: EXPERIMENTS.md 1.7)
+                const unsigned dyn_lds = 8192;
+                const int njobs = plan->first[p + 1] - plan->first[p];
+                hipLaunchKernelGGL((k_ldlt_step<T, NB, true>), dim3(nq + np2 + njobs), dim3(256), dyn_lds, st, nrows, ncols, ld, p0, np2, S, wcur,
+                                   wprev, Winv + (size_t)p * NB * NB, nq, flags, errw, fault, (const int4 *)plan->d_jobs + plan->first[p], (const T *)Wp);
             } else {
                 // The panels go in pairs (0, 1), (2, 3), ...: an odd step p applies panel p - 1 to the next block column alone (the
                 // one step p + 1 factors), the even step p + 1 applies the pair (p - 1, p) to everything from block column p + 2 on

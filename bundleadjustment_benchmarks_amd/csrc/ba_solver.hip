@@ -219,6 +219,8 @@ template <typename T> struct Solver final : SolverBase {
     // A hand-off between workgroups of one launch that timed out (device error word) is survivable: the trial is repeated with the
     // factorisation and the back sweep as one launch per step (nobody waits for anybody), and the solver stays in that mode.
     bool safe_factor = false;
+    ba_ldlt_plan ldlt_plan; // trailing-update jobs of the fused factor (ba_dense.hip.h), device copy in d_ldlt_jobs
+    DevBuf<int> d_ldlt_jobs;
     int fault_rowflag = 0;    // self-test (2): the fused steps' row workgroups stay silent, the panel's wait is short
     double spin_next_s = 0;   // self-test (3): a kernel of that many seconds in front of the next trial
     double watchdog_s = 600;  // no LM row for that long = a hung launch (BA_WATCHDOG_S)
@@ -461,8 +463,12 @@ template <typename T> struct Solver final : SolverBase {
             HIPCHK(hipMemset(d_pcg.p, 0, sizeof(ba_pcg_dev)));
         } else {
             AL(d_slab, (size_t)BA_SLAB * (sx.nchunks > 0 ? sx.nchunks : 1));
-            AL(d_S, (size_t)ld * (Dp + 64)); AL(d_Wp, (size_t)4 * ld * NB); AL(d_Winv, (size_t)((D + NB - 1) / NB) * NB * NB); AL(d_dxc, (size_t)2 * Dp + 2 * NB); /* the solution + the back sweep's hand-over vector */ AL(d_dxp, 3 * M1);
+            AL(d_S, (size_t)ld * (Dp + 64)); AL(d_Wp, (size_t)ba_ldlt_wp_panels(D, NB) * ld * NB); /* the Y history of the fused steps (ba_ldlt_factor) */ AL(d_Winv, (size_t)((D + NB - 1) / NB) * NB * NB); AL(d_dxc, (size_t)2 * Dp + 2 * NB); /* the solution + the back sweep's hand-over vector */ AL(d_dxp, 3 * M1);
             if ((rc = d_flags.alloc((size_t)Dp / NB + 2))) return rc;
+            // the trailing-update schedule of the fused factor: a function of D alone, made and uploaded here, once per solver
+            ldlt_plan = ba_ldlt_make_plan(D + 1, D, NB);
+            if ((rc = d_ldlt_jobs.upload(ldlt_plan.jobs))) return rc;
+            ldlt_plan.d_jobs = d_ldlt_jobs.p;
         }
         AL(d_part_e, (size_t)gE); AL(d_part_pm, (size_t)gM);
         AL(d_part_bs, (size_t)2 * gB); AL(d_part_st, (size_t)4 * gK); AL(d_scal, NSCAL);
@@ -902,7 +908,7 @@ template <typename T> struct Solver final : SolverBase {
     void launch_factor()
     {
         ba_ldlt_factor<T, NB>(st, D + 1, D, ld, d_S.p, d_Wp.p, d_Winv.p, d_flags.p, (int)d_flags.n, d_scal.p + SC_ERR, safe_factor,
-                              safe_factor ? 0 : fault_rowflag);
+                              safe_factor ? 0 : fault_rowflag, &ldlt_plan);
     }
 
     // backward sweep: one data-flow launch (k_ldlt_backflow) while its groups are certainly co-resident
@@ -1199,7 +1205,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         size_t n = 0;
         for (const auto *b : {&d_obs_cam, &d_obs_pt, &d_pt_ptr, &d_pair_hi, &d_pair_lo, &d_pair_chunk_ptr, &d_dchunk_ptr, &d_cam_dchunk_ptr, &d_cam_obs,
-                              &d_qr_pts, &d_flags, &d_pperm, &d_wave_ptr, &d_red_pairs, &d_eb, &d_own_off})
+                              &d_qr_pts, &d_flags, &d_ldlt_jobs, &d_pperm, &d_wave_ptr, &d_red_pairs, &d_eb, &d_own_off})
             n += bytes_of(*b);
         for (const auto *b : {&d_r, &d_Jc, &d_Jp, &d_JcA, &d_U0, &d_gp, &d_V, &d_gc, &d_rec0, &d_dinv0, &d_tvec0, &d_tri0, &d_cam[0], &d_cam[1],
                               &d_pts[0], &d_pts[1], &d_meas, &d_gcg, &d_dslab, &d_rec, &d_dinv, &d_tvec, &d_tri, &d_slab, &d_S, &d_pack, &d_Skeep,

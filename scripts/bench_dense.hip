@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 #include <cmath>
+#include <cstring>
 #include <algorithm>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 int main(int argc, char **argv)
@@ -31,14 +32,18 @@ int main(int argc, char **argv)
     double *S, *Wp, *Winv, *x, *S0; int *flags;
     long long *stamps;
     CK(hipMalloc(&S, sizeof(double) * h.size())); CK(hipMalloc(&S0, sizeof(double) * h.size()));
-    CK(hipMalloc(&Wp, sizeof(double) * (size_t)4 * ld * NB)); CK(hipMalloc(&Winv, sizeof(double) * (size_t)(Dp / NB) * NB * NB));
+    const size_t wpn = (size_t)ba_ldlt_wp_panels(D, NB) * ld * NB; // the Y history of the fused steps
+    CK(hipMalloc(&Wp, sizeof(double) * wpn)); CK(hipMalloc(&Winv, sizeof(double) * (size_t)(Dp / NB) * NB * NB));
     CK(hipMalloc(&x, sizeof(double) * (2 * Dp + 128))); CK(hipMalloc(&stamps, 8 * 64));
     CK(hipMemcpy(S0, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-    CK(hipMemset(Wp, 0, sizeof(double) * (size_t)4 * ld * NB));
+    CK(hipMemset(Wp, 0, sizeof(double) * wpn));
     const int nflags = Dp / NB + 2; CK(hipMalloc(&flags, sizeof(int) * nflags)); CK(hipMemset(flags, 0, sizeof(int) * nflags));
     hipStream_t st; CK(hipStreamCreate(&st));
     hipEvent_t e0, e1, e2, e3; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1)); CK(hipEventCreate(&e2)); CK(hipEventCreate(&e3));
     const int nrows = D + 1, ncols = D, nblk = (ncols + NB - 1) / NB;
+    // the trailing-update schedule of the fused steps (BA_LDLT_UPD_BUDGET / BA_LDLT_UPD_CAP), uploaded once like the solver does
+    auto upload_plan = [&](ba_ldlt_plan pl) { int *d; CK(hipMalloc(&d, sizeof(int) * pl.jobs.size())); CK(hipMemcpy(d, pl.jobs.data(), sizeof(int) * pl.jobs.size(), hipMemcpyHostToDevice)); pl.d_jobs = d; return pl; };
+    const ba_ldlt_plan plan = upload_plan(ba_ldlt_make_plan(nrows, ncols, NB));
     float tp = 0, tu = 0, tb = 0, tot = 0;
     std::vector<double> xs_h(D);
     const int reps = 5;
@@ -47,7 +52,7 @@ int main(int argc, char **argv)
     for (int rep = 0; rep < reps + 1; rep++) {
         CK(hipMemcpyAsync(S, S0, sizeof(double) * h.size(), hipMemcpyDeviceToDevice, st));
         CK(hipEventRecord(e0, st));
-        if (fused) ba_ldlt_factor<double, NB>(st, nrows, ncols, ld, S, Wp, Winv, flags, nflags); // the product's launch sequence
+        if (fused) ba_ldlt_factor<double, NB>(st, nrows, ncols, ld, S, Wp, Winv, flags, nflags, nullptr, false, 0, &plan); // the product's launch sequence
         else for (int p = 0; p < nblk; p++) {
             const int p0 = p * NB, below = nrows - (p0 + NB), g = below > 0 ? (below + 63) / 64 : 1;
             hipLaunchKernelGGL((k_ldlt_panel<double, NB>), dim3(g), dim3(256), 0, st, nrows, ncols, ld, p0, S, Wp, Winv + (size_t)p * NB * NB, flags, nflags);
@@ -72,6 +77,46 @@ int main(int argc, char **argv)
     CK(hipMemcpy(xs_h.data(), x, sizeof(double) * D, hipMemcpyDeviceToHost));
     { double rn = 0, bn = 0; for (int r = 0; r < D; r++) { double a = 0; for (int c = 0; c < D; c++) a += (c <= r ? h[(size_t)c * ld + r] : h[(size_t)r * ld + c]) * xs_h[c]; const double b = h[(size_t)r * ld + D]; rn += (a - b) * (a - b); bn += b * b; }
       printf("%s: D=%d factor %.3f ms  backsweep %.3f ms  residual %.2e\n", fused ? "fused look-ahead" : "separate launches", D, tot / reps, tb / reps, std::sqrt(rn / bn)); }
+    }
+    if (argc > 2 && atoi(argv[2]) == -2) {
+        // Sweep of the trailing-update schedule (bench_dense.bin <D> -2 [rounds]): budget (+ slope per launch) x cap, variants interleaved round by round, median over the rounds of the mean of `reps` factorisations; every variant's factor is
+        // compared bit for bit with the textbook order's (variant 0).
+        struct V { long long budget; int cap; long long slope; };
+        std::vector<V> vs = {{BA_LDLT_BUDGET_UNBOUNDED, 1, 0}};
+        for (int cap : {2, 3, 4}) for (long long b : {0, 100, 250, 300, 350, 400, 450}) vs.push_back({b, cap, 0});
+        for (int cap : {2, 3, 4}) { vs.push_back({200, cap, 8}); vs.push_back({250, cap, 6}); vs.push_back({400, cap, -6}); }
+        std::vector<ba_ldlt_plan> pls;
+        for (const V &v : vs) pls.push_back(upload_plan(ba_ldlt_make_plan(nrows, ncols, NB, v.budget, v.cap, v.slope)));
+        const int rounds = argc > 3 ? atoi(argv[3]) : 7;
+        std::vector<std::vector<float>> ms(vs.size());
+        std::vector<double> ref(h.size()), got(h.size());
+        std::vector<int> equal(vs.size(), -1);
+        for (int round = 0; round < rounds; round++)
+            for (size_t k = 0; k < vs.size(); k++) {
+                float acc = 0;
+                for (int rep = 0; rep < reps + 1; rep++) {
+                    CK(hipMemcpyAsync(S, S0, sizeof(double) * h.size(), hipMemcpyDeviceToDevice, st));
+                    CK(hipEventRecord(e0, st));
+                    ba_ldlt_factor<double, NB>(st, nrows, ncols, ld, S, Wp, Winv, flags, nflags, nullptr, false, 0, &pls[k]);
+                    CK(hipEventRecord(e1, st));
+                    CK(hipStreamSynchronize(st));
+                    float a; CK(hipEventElapsedTime(&a, e0, e1));
+                    if (rep) acc += a;
+                }
+                ms[k].push_back(acc / reps);
+                if (round == 0) {
+                    CK(hipMemcpy(k ? got.data() : ref.data(), S, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+                    equal[k] = k ? memcmp(got.data(), ref.data(), sizeof(double) * h.size()) == 0 : 1;
+                }
+            }
+        for (size_t k = 0; k < vs.size(); k++) {
+            std::sort(ms[k].begin(), ms[k].end());
+            size_t nj = pls[k].jobs.size() / 4 - 1; int mx = 0;
+            for (int p = 1; p < nblk; p++) mx = std::max(mx, pls[k].first[p + 1] - pls[k].first[p]);
+            printf("sweep D=%d budget %lld slope %lld cap %d: jobs %zu (most per launch %d)  factor median %.4f ms  min %.4f  max %.4f  bit-equal %d\n", D,
+                   vs[k].budget >= BA_LDLT_BUDGET_UNBOUNDED ? -1ll : vs[k].budget, vs[k].slope, vs[k].cap, nj, mx, ms[k][ms[k].size() / 2], ms[k].front(), ms[k].back(), equal[k]);
+        }
+        return 0;
     }
     // panel-only and update-only timings at p0 = 0
     CK(hipMemcpy(S, S0, sizeof(double) * h.size(), hipMemcpyDeviceToDevice));
@@ -123,13 +168,12 @@ int main(int argc, char **argv)
         hipEvent_t f0, f1; CK(hipEventCreate(&f0)); CK(hipEventCreate(&f1));
         for (int p = 0; p <= 8 && p < nblk; p++) {
             const int p0 = p * NB, below = nrows - (p0 + NB), g = below > 0 ? (below + 63) / 64 : 1;
-            double *wcur = Wp + (size_t)(p & 1) * ld * NB, *wprev = Wp + (size_t)((p + 1) & 1) * ld * NB;
+            double *wcur = Wp + (size_t)p * ld * NB, *wprev = Wp + (size_t)(p ? p - 1 : 0) * ld * NB;
             if (p == 0) { hipLaunchKernelGGL((k_ldlt_panel<double, NB>), dim3(g), dim3(256), 0, st, nrows, ncols, ld, p0, S, wcur, Winv, flags, nflags); continue; }
             const int nt = (nrows - p0 + 63) / 64, ntc = (ncols - p0 + 63) / 64;
-            int nupd = 0;
-            for (int ti = 1; ti < nt; ti++) nupd += std::min(ti, ntc - 1);
+            const int nupd = plan.first[p + 1] - plan.first[p]; (void)nt; (void)ntc;
             if (p == 8) CK(hipEventRecord(f0, st));
-            hipLaunchKernelGGL((k_ldlt_step<double, NB, true>), dim3(3 * g + nupd), dim3(256), 8192, st, nrows, ncols, ld, p0, 2 * g, S, wcur, wprev, Winv + (size_t)p * NB * NB, g, flags, (double *)nullptr);
+            hipLaunchKernelGGL((k_ldlt_step<double, NB, true>), dim3(3 * g + nupd), dim3(256), 8192, st, nrows, ncols, ld, p0, 2 * g, S, wcur, wprev, Winv + (size_t)p * NB * NB, g, flags, (double *)nullptr, 0, (const int4 *)plan.d_jobs + plan.first[p], (const double *)Wp);
             if (p == 8) CK(hipEventRecord(f1, st));
         }
         CK(hipStreamSynchronize(st));

@@ -164,11 +164,12 @@ def reduced(S_base, rhs_base, d):
     return np.asarray(S_base).astype(LD) + d["S"], np.asarray(rhs_base).astype(LD) + d["g"]
 
 
-def standard_constraints(N, cam_idx, pt_idx, cam15, Vdiag, seed=11, kappa_t=10.0, kappa_r=1.0):
+def standard_constraints(N, cam_idx, pt_idx, cam15, Vdiag, seed=11, kappa_t=10.0, kappa_r=1.0, angle=0.05):
     """The constraint set of the GPU tests: an odometry chain (a, a + 1) over all cameras plus one hub camera tied to 40 others (to all
     of them if N <= 41; pairs the chain already holds are left out).  The hub is the camera that shares no point with the most others,
     so that pairs without a common point occur whenever the problem has one.  R0, t0: the start state's relative pose perturbed by a
-    rotation of 0.05 rad about a seeded axis and by 1 % of |t_ab| in a seeded direction.  Information, sized like
+    rotation of `angle` rad (one value, or one per constraint, cycled if shorter than the list; 0.05 by default: the cot-series switch
+    of ba_relpose_eval) about a seeded axis and by 1 % of |t_ab| in a seeded direction.  Information, sized like
     prior_checks.standard_priors: kappa x the median own diagonal of the blocks joined (Vdiag [N, 9] = diag of sum Jc'Jc), i.e.
     sigma_t = 1 / sqrt(kappa_t median V_TT), sigma_r = 1 / sqrt(kappa_r median V_omega omega), kappa_t = 10 (an upper-triangular L_t with
     off-diagonals 0.3 / sigma), kappa_r = 1 (isotropic), both inside [1e-2, 1e2].  Returns (Constraints, dict(sigma_t, sigma_r, hub,
@@ -194,10 +195,11 @@ def standard_constraints(N, cam_idx, pt_idx, cam15, Vdiag, seed=11, kappa_t=10.0
     st = 1 / np.sqrt(kappa_t * np.median(Vdiag[:, :3]))
     sr = 1 / np.sqrt(kappa_r * np.median(Vdiag[:, 3:6]))
     R0, t0 = np.zeros((n, 3, 3)), np.zeros((n, 3))
+    ang = np.resize(np.asarray(angle, np.float64), n)
     for q, (a, b) in enumerate(pairs):
         Rab, tab = relative_pose(cam15, a, b)
         ax, dr = rng.standard_normal(3), rng.standard_normal(3)
-        R0[q] = (rodrigues(0.05 * ax / np.linalg.norm(ax)) @ Rab).astype(np.float64)
+        R0[q] = (rodrigues(ang[q] * ax / np.linalg.norm(ax)) @ Rab).astype(np.float64)
         t0[q] = (tab + 0.01 * np.sqrt(float((tab * tab).sum())) * dr / np.linalg.norm(dr)).astype(np.float64)
     Lt = np.tile(np.array([[1.0, 0.3, 0.3], [0, 1.0, 0.3], [0, 0, 1.0]]) / st, (n, 1, 1))
     Lr = np.tile(np.eye(3) / sr, (n, 1, 1))

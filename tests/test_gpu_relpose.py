@@ -56,19 +56,24 @@ def _problem(ba, name, prob21, prob39):
     return _PROBLEMS[name]
 
 
-def _constraints(ba, O, pg, name):
-    """standard_constraints of a problem, sized from the fp64 CHOLESKY linearisation at the start state, once per problem."""
-    if name not in _CONSTRAINTS:
+WIDE_ANGLES = (1e-9, 5e-4, 1e-2, 1.0, 2.5, float(np.pi) - 1e-3)  # both series, both closed forms, c < 0, the neighbourhood of pi
+
+
+def _constraints(ba, O, pg, name, wide=False):
+    """standard_constraints of a problem, sized from the fp64 CHOLESKY linearisation at the start state, once per problem.  wide: the
+    residual rotations cycle through WIDE_ANGLES instead of 0.05 rad."""
+    key = (name, wide)
+    if key not in _CONSTRAINTS:
         po = sorted_oracle_problem(O, pg)
         s = ba.Solver(pg, ba.CHOLESKY, ba.F64)
         s.linearize()
         V = np.zeros((pg.N, 9))
         np.add.at(V, po.cam_idx, (s.get(ba.GET_JC).reshape(-1, 2, 9) ** 2).sum(axis=1))
-        cs, info = RC.standard_constraints(pg.N, po.cam_idx, po.pt_idx, s.get(ba.GET_CAMS), V)
+        cs, info = RC.standard_constraints(pg.N, po.cam_idx, po.pt_idx, s.get(ba.GET_CAMS), V, **(dict(angle=WIDE_ANGLES) if wide else {}))
         print("RELPOSE sigmas %s trans %.3e rot %.3e (%d constraints, hub %d, %d pairs without a common point, at most %d common points)"
-              % (name, info["sigma_t"], info["sigma_r"], info["n"], info["hub"], info["n_no_common"], info["max_common"]))
-        _CONSTRAINTS[name] = (cs, info)
-    return _CONSTRAINTS[name]
+              % (name + ("-wide" if wide else ""), info["sigma_t"], info["sigma_r"], info["n"], info["hub"], info["n_no_common"], info["max_common"]))
+        _CONSTRAINTS[key] = (cs, info)
+    return _CONSTRAINTS[key]
 
 
 def _rounded(cs, scalar):
@@ -118,9 +123,20 @@ LIN_CASES = [("p21", "plain"), ("ragged", "plain"), ("p39", "plain"), ("syn2", "
 def test_linearisation_matches_the_yardstick(ba, O, gpu_ok, prob21, prob39, prob, variant, skind, scalar):
     """Energy, the two constraint energies, BA_GET_GRAD and max diag J'J.  `priors`: Huber + weights + standard_priors on top; `mask`:
     the pose of chain camera 3 and T1 of the hub's first neighbour held constant."""
+    _check_linearisation(ba, O, prob21, prob39, prob, variant, skind, scalar, False)
+
+
+@pytest.mark.parametrize("skind,scalar", [(2, 0), (2, 1), (5, 0)], ids=["cholesky-f64", "cholesky-f32", "iterschur-f64"])
+def test_linearisation_matches_the_yardstick_at_wide_angles(ba, O, gpu_ok, prob21, prob39, skind, scalar):
+    """The same quantities under the same bounds on problem-21 with the constraints' residual rotations cycling through WIDE_ANGLES:
+    every branch of ba_relpose_eval through the C ABI (the standard set holds all of them at 0.05 rad)."""
+    _check_linearisation(ba, O, prob21, prob39, "p21", "plain", skind, scalar, True)
+
+
+def _check_linearisation(ba, O, prob21, prob39, prob, variant, skind, scalar, wide):
     pg = _problem(ba, prob, prob21, prob39)
     po = sorted_oracle_problem(O, pg)
-    cs, info = _constraints(ba, O, pg, prob)
+    cs, info = _constraints(ba, O, pg, prob, wide)
     if prob == "syn2":
         assert len(cs) == 1
     if prob == "syn257":
@@ -138,7 +154,7 @@ def test_linearisation_matches_the_yardstick(ba, O, gpu_ok, prob21, prob39, prob
     Y = _yardstick(O, po, None if pr is None else _solver_priors(pr, scalar), _rounded(cs, scalar), s.get(ba.GET_CAMS), s.get(ba.GET_POINTS),
                    kind, scale, wy, cm, None)
     tol = TOL[scalar]
-    ck = Checker("lin[%s,%s,%s,%s]" % (prob, variant, ba.KIND_NAMES[skind], SN[scalar]))
+    ck = Checker("lin[%s,%s,%s,%s]" % (prob, "wide" if wide else variant, ba.KIND_NAMES[skind], SN[scalar]))
     ck("energy", abs(energy - float(Y["energy"])) / float(Y["energy"]), tol["energy"])
     ce = s.relative_pose_energy()
     for q, name in enumerate(("rot", "trans")):
@@ -179,9 +195,19 @@ def test_trial_matches_the_yardstick(ba, O, gpu_ok, prob21, prob39, prob, scalar
     """CHOLESKY with keep_intermediates at lambda = 1e-6 and 1e-2 x max diag J'J: the kept S and rhs against the quad reduced system of
     the (prior-augmented) observations at the GPU's own J plus relpose_checks.direct; the block of a pair without a common point is
     H_ab alone; eta of the step, e_test and rho_scale."""
+    _check_trial(ba, O, prob21, prob39, prob, scalar, priors, False)
+
+
+@pytest.mark.parametrize("scalar", [0, 1], ids=["f64", "f32"])
+def test_trial_matches_the_yardstick_at_wide_angles(ba, O, gpu_ok, prob21, prob39, scalar):
+    """The same quantities under the same bounds on problem-21 with the constraints' residual rotations cycling through WIDE_ANGLES."""
+    _check_trial(ba, O, prob21, prob39, "p21", scalar, False, True)
+
+
+def _check_trial(ba, O, prob21, prob39, prob, scalar, priors, wide):
     pg = _problem(ba, prob, prob21, prob39)
     po = sorted_oracle_problem(O, pg)
-    cs0, info = _constraints(ba, O, pg, prob)
+    cs0, info = _constraints(ba, O, pg, prob, wide)
     cs = _rounded(cs0, scalar)
     pr0 = _priors(ba, O, pg, prob) if priors else PC.Priors()
     pr = _solver_priors(pr0, scalar)
@@ -193,7 +219,7 @@ def test_trial_matches_the_yardstick(ba, O, gpu_ok, prob21, prob39, prob, scalar
     d = _direct(cs, po.N, cams)
     g = s.get(ba.GET_GRAD)
     M, N = po.M, po.N
-    ck = Checker("trial[%s,%s]" % (prob, SN[scalar]))
+    ck = Checker("trial[%s%s,%s]" % (prob, ",wide" if wide else "", SN[scalar]))
     dt = F64 if scalar == 0 else np.float32
     lone = None
     assert info["n_no_common"] > 0 and info["max_common"] > 1, info  # (problem-21, -39 and the ragged one all have such pairs)
@@ -453,6 +479,24 @@ def test_covariance_with_constraints(ba, O, gpu_ok, prob21):
 
 
 # ---- 6. behaviour --------------------------------------------------------------------------------------------------------------------------
+def _lm_yardstick(O, po, cs, cams0, pts0):
+    """relpose_checks.lm_dense on the dense normal equations of the observation rows of loss_checks (plain least squares) and the
+    constraint rows, from the start state: (the state it reaches, its energy)."""
+    M, N = po.M, po.N
+
+    def fun(x):
+        cam, pts = x
+        Y = LC.model(O, po, cam.astype(F64), pts.astype(F64), LC.TRIVIAL, 1.0, None)
+        J = np.zeros((2 * po.K, 3 * M + 9 * N), LD)
+        for k in range(po.K):
+            J[2 * k:2 * k + 2, 3 * po.pt_idx[k]:3 * po.pt_idx[k] + 3] = Y["Jp"][k]
+            J[2 * k:2 * k + 2, 3 * M + 9 * po.cam_idx[k]:3 * M + 9 * po.cam_idx[k] + 9] = Y["Jc"][k]
+        Jr, er = RC.stacked(cs, N, cam)
+        Jr = np.concatenate([np.zeros((len(er), 3 * M), LD), Jr], axis=1)
+        return np.concatenate([J, Jr]), np.concatenate([Y["e"].ravel(), er])
+    return RC.lm_dense(fun, (np.array(cams0, LD).reshape(-1, 15), np.array(pts0, LD).reshape(-1, 3)), lambda x, dx: PC.retract(x[0], x[1], dx), max_iter=200)
+
+
 @pytest.mark.parametrize("skind", [2, 5], ids=["cholesky", "iterschur"])
 def test_two_cameras_reach_the_constrained_baseline(ba, O, gpu_ok, prob21, prob39, skind):
     """Two cameras, one constraint with t0 = 2 t_ab(start), R0 = R_ab(start) and large information (1e3 x the chain's), plain least
@@ -474,24 +518,46 @@ def test_two_cameras_reach_the_constrained_baseline(ba, O, gpu_ok, prob21, prob3
     assert r["trace"][0, 2] == e0
     t1 = RC.relative_pose(s.get(ba.GET_CAMS), 0, 1)[1]
     got = float(np.sqrt(((t1 - cs.t0[0]) ** 2).sum()) / np.linalg.norm(cs.t0[0]))
-    M, N = po.M, po.N
-
-    def fun(x):
-        cam, pts = x
-        Y = LC.model(O, po, cam.astype(F64), pts.astype(F64), LC.TRIVIAL, 1.0, None)
-        J = np.zeros((2 * po.K, 3 * M + 9 * N), LD)
-        for k in range(po.K):
-            J[2 * k:2 * k + 2, 3 * po.pt_idx[k]:3 * po.pt_idx[k] + 3] = Y["Jp"][k]
-            J[2 * k:2 * k + 2, 3 * M + 9 * po.cam_idx[k]:3 * M + 9 * po.cam_idx[k] + 9] = Y["Jc"][k]
-        Jr, er = RC.stacked(cs, N, cam)
-        Jr = np.concatenate([np.zeros((len(er), 3 * M), LD), Jr], axis=1)
-        return np.concatenate([J, Jr]), np.concatenate([Y["e"].ravel(), er])
-    x, E = RC.lm_dense(fun, (np.array(cams0, LD).reshape(-1, 15), np.array(pts0, LD).reshape(-1, 3)), lambda x, dx: PC.retract(x[0], x[1], dx), max_iter=200)
+    x, E = _lm_yardstick(O, po, cs, cams0, pts0)
     t2 = RC.relative_pose(x[0], 0, 1)[1]
     yard = float(np.sqrt(((t2 - cs.t0[0]) ** 2).sum()) / np.linalg.norm(cs.t0[0]))
     print("RELPOSE behaviour[%s] |t_ab - t0| / |t0| start 5.000e-01 gpu %.3e yardstick_lm %.3e energies gpu %.9g lm %.9g" % (ba.KIND_NAMES[skind], got, yard, r["energy"], float(E)))
     ck = Checker("behaviour[%s]" % ba.KIND_NAMES[skind])
     ck("baseline_misfit(yardstick %.1e)" % yard, got, 10 * yard)
+    ck.done()
+
+
+@pytest.mark.parametrize("angle", [0.3, 3.0], ids=["0.3rad", "3.0rad"])
+def test_two_cameras_reach_the_constrained_rotation(ba, O, gpu_ok, prob21, prob39, angle):
+    """Two cameras, one constraint with t0 = t_ab(start), R0 a rotation of `angle` away from R_ab(start) and stiff rotation information
+    (1e3 x the chain's), plain least squares, CHOLESKY fp64: after ba_minimize |phi| = |Log(R_ab R0')| is below 10 x what the yardstick's
+    own long-double LM reaches on the same problem, and below 1e-3.  The start lies above both switches of ba_relpose_eval (theta = 0.05,
+    sin(theta) = 1e-3; from 3.0 rad also in the quadrant c < 0) and the end state below both; which iterates the run passes on its way
+    is not read.  (The yardstick's LM, 200 plain iterations, stops at a higher energy than ba_minimize: its |phi| is a loose target.)"""
+    pg = _problem(ba, "syn2", prob21, prob39)
+    po = sorted_oracle_problem(O, pg)
+    cs0, _ = _constraints(ba, O, pg, "syn2")
+    s = ba.Solver(pg, ba.CHOLESKY, ba.F64)
+    s.set_loss(ba.LOSS_TRIVIAL)
+    cams0, pts0 = s.get(ba.GET_CAMS), s.get(ba.GET_POINTS)
+    Rab, tab = RC.relative_pose(cams0, 0, 1)
+    ax = np.random.default_rng(23).standard_normal(3)
+    R0 = (PC.rodrigues(angle * ax / np.linalg.norm(ax)) @ Rab).astype(F64)
+    cs = RC.Constraints([(0, 1)], R0, tab.astype(F64), 1e3 * cs0.Lr[0], cs0.Lt[0])
+    cs.apply(s)
+    e0, _ = s.linearize()
+    r = s.minimize(max_trials=200)
+    assert r["trace"][0, 2] == e0
+    norm = lambda v: float(np.sqrt((v * v).sum()))
+    start = norm(RC.residuals(cs, cams0)[2][0])
+    got = norm(RC.residuals(cs, s.get(ba.GET_CAMS))[2][0])
+    x, E = _lm_yardstick(O, po, cs, cams0, pts0)
+    yard = norm(RC.residuals(cs, x[0])[2][0])
+    print("RELPOSE rotation[%s] |phi| start %.3e gpu %.3e yardstick_lm %.3e energies gpu %.9g lm %.9g" % (angle, start, got, yard, r["energy"], float(E)))
+    assert abs(start - angle) < 1e-9
+    ck = Checker("rotation[%s]" % angle)
+    ck("rotation_misfit(yardstick %.1e)" % yard, got, 10 * yard)
+    ck("end_state_below_both_switches", got, 1e-3)
     ck.done()
 
 

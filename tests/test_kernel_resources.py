@@ -52,3 +52,14 @@ def test_qr_harness_builds_with_the_library_flags(tmp_path):
     hipcc, flags = QH.makefile_flags()
     assert {"--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-amdgpu-mfma-vgpr-form"} <= set(flags), flags
     assert os.path.getsize(QH.build(tmp_path)) > 0
+
+
+def test_relpose_harness_builds_with_the_library_flags(tmp_path):
+    """tests/relpose_harness.hip (test_gpu_relpose_kernels.py's driver of ba_relpose.hip.h) compiles with csrc/Makefile's own flags, and
+    its CSR of the cameras' incident constraints is the one ba_solver_set_relative_poses builds: per camera in list order,
+    2 * constraint + side."""
+    import numpy as np
+    import relpose_harness as RH
+    assert os.path.getsize(RH.build(tmp_path)) > 0
+    ptr, inc = RH.csr(4, [(2, 0), (0, 1), (1, 2)])
+    assert np.array_equal(ptr, [0, 2, 4, 6, 6]) and np.array_equal(inc, [1, 2, 3, 4, 0, 5])

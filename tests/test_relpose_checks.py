@@ -175,6 +175,32 @@ def test_standard_constraints_and_the_long_double_lm():
     assert float(E) <= 1e-30, float(E)
 
 
+def test_standard_constraints_take_the_angle_per_constraint():
+    """angle = 0.05 written out is the default in every bit; a list of angles is cycled over the constraints and each one is the
+    residual rotation's angle (pi - 1e-3 to 1e-12 relative: Log's eps / (pi - theta) in long double is 5e-17)."""
+    rng = np.random.default_rng(19)
+    N = 12
+    cam = np.zeros((N, 15))
+    for a in range(N):
+        cam[a, :9] = PC.rodrigues(_unit(rng) * rng.uniform(0.3, 2.5)).astype(np.float64).reshape(-1)
+        cam[a, 9:12] = rng.standard_normal(3)
+    pt = np.repeat(np.arange(30), 2).astype(np.int32)
+    ci = (np.arange(60) % N).astype(np.int32)
+    base, _ = RC.standard_constraints(N, ci, pt, cam, np.ones((N, 9)))
+    same, _ = RC.standard_constraints(N, ci, pt, cam, np.ones((N, 9)), angle=0.05)
+    for k in ("pairs", "R0", "t0", "Lr", "Lt"):
+        assert np.array_equal(getattr(base, k), getattr(same, k)), k
+    angles = [1e-9, 5e-4, 1e-2, 1.0, 2.5, np.pi - 1e-3]
+    wide, _ = RC.standard_constraints(N, ci, pt, cam, np.ones((N, 9)), angle=angles)
+    assert np.array_equal(wide.pairs, base.pairs) and np.array_equal(wide.t0, base.t0) and len(wide) > len(angles)
+    _, _, ph = RC.residuals(wide, cam)
+    th = np.sqrt((ph * ph).sum(axis=1)).astype(np.float64)
+    # R0 is rounded to double: an absolute 1e-16 in the rotation, 1e-7 of the angle 1e-9
+    assert np.allclose(th, np.resize(angles, len(wide)), rtol=1e-9, atol=1e-15)
+    one, _ = RC.standard_constraints(N, ci, pt, cam, np.ones((N, 9)), angle=np.full(len(base), 0.05))
+    assert np.array_equal(one.R0, base.R0)
+
+
 def test_header_binding_and_library_declare_the_constraints(ba):
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ba_mi355x.h")).read(), flags=re.S)  # (without the comments)
     dbl = r"const\s+double\s*\*\s*"

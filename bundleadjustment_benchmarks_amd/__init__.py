@@ -41,7 +41,7 @@ EXPORTS = [
     "ba_version", "ba_shard_plan", "ba_problem_save_cache", "ba_problem_load_cache", "ba_solver_selftest",
     "ba_comm_unique_id", "ba_comm_id_via_file", "ba_comm_id_file_done", "ba_solver_comm_init", "ba_solver_recoveries",
     "ba_solver_set_pcg", "ba_solver_pcg_stats", "ba_solver_device_bytes", "ba_solver_set_constant", "ba_problem_gauge_mask",
-    "ba_solver_covariance_compute", "ba_solver_covariance_get", "ba_solver_covariance_timing",
+    "ba_solver_covariance_compute", "ba_solver_covariance_get", "ba_solver_covariance_timing", "ba_solver_covariance_pcg",
     "ba_solver_set_loss", "ba_solver_set_obs_weights",
     "ba_solver_set_point_priors", "ba_solver_set_centre_priors", "ba_solver_set_intrinsics_priors", "ba_solver_prior_energy",
     "ba_solver_set_relative_poses", "ba_solver_relative_pose_energy",
@@ -72,6 +72,11 @@ class Timing(C.Structure):
 class PCGStats(C.Structure):
     _fields_ = [("solves", C.c_longlong), ("total_iters", C.c_longlong), ("last_iters", C.c_int), ("last_converged", C.c_int),
                 ("last_rel_residual", C.c_double)]
+
+
+class CovPCGStats(C.Structure):
+    _fields_ = [("columns", C.c_longlong), ("batches", C.c_longlong), ("total_iters", C.c_longlong), ("max_iters", C.c_int),
+                ("unconverged", C.c_int), ("worst_rel_residual", C.c_double), ("ms", C.c_double)]
 
 
 TRIAL_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double)
@@ -140,6 +145,8 @@ def lib():
         L.ba_solver_covariance_compute.argtypes = [C.c_void_p, C.c_double]
         L.ba_solver_covariance_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ba_solver_covariance_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_covariance_pcg.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
         L.ba_solver_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.ba_solver_set_obs_weights.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_point_priors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -500,6 +507,26 @@ class Solver:
         pc = np.empty((len(pts), 3, 3))
         _chk(lib().ba_solver_covariance_get(self._h, len(pairs), _p(pairs), _p(cc), len(pts), _p(pts), _p(pc)), "ba_solver_covariance_get")
         return cc, pc
+
+    def covariance_pcg(self, lam=0.0, cam_pairs=None, cams=None, points=None, max_iter=0, rel_tol=0.0):
+        """ITERSCHUR: covariance blocks without forming S, by a PCG on nine right-hand sides at a time (ba_solver_covariance_pcg; F64,
+        one shard).  The arguments of covariance(); max_iter = 0 / rel_tol = 0 take the values of set_pcg.  Returns (camera blocks,
+        point blocks, stats): stats["unconverged"] counts the columns that ended at max_iter (no error: look at it), and
+        stats["worst_rel_residual"] is the largest |b - S x| / |b| of a column.  Raises BAError: code ERR_SINGULAR when a point block or a
+        camera's diagonal block is not positive definite, or a search direction has p'Sp <= 0."""
+        if cam_pairs is not None and cams is not None:
+            raise ValueError("give cam_pairs or cams, not both")
+        if cams is not None:
+            cams = np.asarray(cams, np.int32).reshape(-1)
+            cam_pairs = np.stack([cams, cams], axis=1)
+        pairs = np.zeros((0, 2), np.int32) if cam_pairs is None else np.ascontiguousarray(cam_pairs, np.int32).reshape(-1, 2)
+        pts = np.zeros(0, np.int32) if points is None else np.ascontiguousarray(points, np.int32).reshape(-1)
+        cc = np.empty((len(pairs), 9, 9))
+        pc = np.empty((len(pts), 3, 3))
+        st = CovPCGStats()
+        _chk(lib().ba_solver_covariance_pcg(self._h, float(lam), int(max_iter), float(rel_tol), len(pairs), _p(pairs), _p(cc), len(pts), _p(pts),
+                                            _p(pc), C.byref(st)), "ba_solver_covariance_pcg")
+        return cc, pc, {k: getattr(st, k) for k, _ in CovPCGStats._fields_}
 
     def covariance_timing(self):
         """Device ms: (assembly, factorisation, inverse) of the last covariance compute, the point kernel of the last read of points."""

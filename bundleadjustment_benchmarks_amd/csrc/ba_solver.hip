@@ -12,6 +12,7 @@
 #include "ba_qr.hip.h"
 #include "ba_pcg.hip.h"
 #include "ba_cov.hip.h"
+#include "ba_pcg_multi.hip.h"
 #include "ba_prior.hip.h"
 #include "ba_relpose.hip.h"
 
@@ -109,6 +110,8 @@ struct SolverBase {
     virtual int cov_compute(double lambda) = 0;
     virtual int cov_get(int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov) = 0;
     virtual int cov_timing(double *ms4) = 0;
+    virtual int cov_pcg(double lambda, int max_iter, double rel_tol, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids,
+                        double *pt_cov, ba_cov_pcg_stats *stats) = 0;
     bool poisoned = false; // the watchdog gave up on a launch that never finished: every later call fails, nothing is freed
     int recoveries = 0;    // trials repeated through the launch-per-step factorisation after a hand-off time-out
     ba_allreduce_fn ar_fn = nullptr;
@@ -1117,13 +1120,14 @@ template <typename T> struct Solver final : SolverBase {
 
     // segment A behind k_elim_chol: block-Jacobi preconditioner, reduced rhs, g_c for the retraction's rho terms, x_0 = 0 and the
     // recurrence's start (p_{-1} = 0, z_0, slot-0 partials, |rhs|^2)
-    void launch_pcg_blocks()
+    // (Bm, rhs, gc_out: the trial's own buffers unless ba_solver_covariance_pcg hands in its scratch)
+    void launch_pcg_blocks(T *Bm = nullptr, T *rhs = nullptr, T *gc_out = nullptr)
     {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_prec_chunks<T>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p, d_obs_pt.p,
                                d_rec.p, d_tvec.p, Ml, d_dslab.p);
         hipLaunchKernelGGL((k_pcg_prec_reduce<T>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
-                           d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, d_pcg_M.p, d_pcg_b.p, d_gcg.p);
+                           d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, Bm ? Bm : d_pcg_M.p, rhs ? rhs : d_pcg_b.p, gc_out ? gc_out : d_gcg.p);
     }
     void launch_pcg_prep()
     {
@@ -1214,7 +1218,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes();
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1354,6 +1358,233 @@ template <typename T> struct Solver final : SolverBase {
     {
         for (int q = 0; q < 4; q++) ms4[q] = cov_ms[q];
         return BA_OK;
+    }
+
+    // ---- covariance blocks by multi-column PCG (ba_solver_covariance_pcg; ba_pcg_multi.hip.h) ---------------------
+    // Work vectors of its own, allocated by the first call: x, r, z, p, y and the right-hand sides B ([9 N][9] each), the point pass
+    // ([3 Ml][9]), the chunk slab ([ndchunks][9][9]), B_a^-1 ([N][81]), three lists of workgroup partials ([gm][9]) and the state.  The
+    // trial's own vectors (d_dxc, d_pcg_*) are not touched; what the call spends are the elimination's records and d_dslab.
+    // (double only: the members below are instantiated for the fp64 solver alone, from cov_pcg's fp64 branch)
+    DevBuf<double> d_mc_vec, d_mc_w, d_mc_slab, d_mc_M, d_mc_part;
+    DevBuf<ba_mc_dev> d_mc;
+    int mc_gm() const { return (N + BA_MC_CPB - 1) / BA_MC_CPB; }
+    size_t mc_bytes() const { return bytes_of(d_mc_vec) + bytes_of(d_mc_w) + bytes_of(d_mc_slab) + bytes_of(d_mc_M) + bytes_of(d_mc_part) + bytes_of(d_mc); }
+    void mc_release() { d_mc_vec.release(); d_mc_w.release(); d_mc_slab.release(); d_mc_M.release(); d_mc_part.release(); d_mc.release(); }
+    // one call: where its vectors are, its stopping rule, the mask in force, the statistics so far
+    struct McRun {
+        double *x, *r, *z, *p, *y, *b, *part_rz, *part_rr, *part_py;
+        int gm, max_iter;
+        double tol2;
+        const unsigned short *cmask;
+        const unsigned char *pfix;
+        ba_cov_pcg_stats acc;
+    };
+    int mc_begin(int max_iter, double rel_tol, McRun &c)
+    {
+        int rc;
+        const size_t DV = (size_t)D * BA_MC_NR;
+        const int gm = mc_gm();
+        if (!d_mc.p) {
+            if ((rc = d_mc_vec.alloc(6 * DV)) || (rc = d_mc_w.alloc((size_t)27 * (Ml > 0 ? Ml : 1))) ||
+                (rc = d_mc_slab.alloc((size_t)81 * (sx.ndchunks > 0 ? sx.ndchunks : 1))) || (rc = d_mc_M.alloc((size_t)81 * N)) ||
+                (rc = d_mc_part.alloc((size_t)3 * gm * BA_MC_NR)) || (rc = d_mc.alloc(1))) {
+                (void)hipGetLastError(); // (the solver stays usable)
+                mc_release();
+                return rc;
+            }
+        }
+        double *v = d_mc_vec.p, *pt = d_mc_part.p;
+        c = McRun{v, v + DV, v + 2 * DV, v + 3 * DV, v + 4 * DV, v + 5 * DV, pt, pt + (size_t)gm * BA_MC_NR, pt + 2 * (size_t)gm * BA_MC_NR, gm, max_iter,
+                  rel_tol * rel_tol, masked ? (const unsigned short *)d_cmask.p : nullptr, masked ? (const unsigned char *)d_pfix.p : nullptr,
+                  ba_cov_pcg_stats{}};
+        return BA_OK;
+    }
+    // Once per call: the elimination at lambda and the block-Jacobi blocks B_a as a trial forms them (launch_pcg_blocks into this call's
+    // buffers: the reduced rhs of the last trial, BA_GET_RHS, stays where it is), every free point's block and every B_a positive definite
+    int mc_prepare(double lambda, const McRun &c)
+    {
+        int rc;
+        ba_mc_dev *ms = d_mc.p;
+        HIPCHK(hipMemsetAsync(&ms->flag, 0, sizeof(int), st));
+        if ((rc = set_lambda((T)lambda))) return rc;
+        HIPCHK(hipEventRecord(ev[EV_T0], st));
+        launch_eliminate();
+        if (masked && d_pfix.p)
+            hipLaunchKernelGGL((k_cov_fixed_records<T>), dim3((std::max(Kl, Ml) + 255) / 256), dim3(256), 0, st, Kl, Ml, (int)BA_REC, (const int *)d_obs_pt.p,
+                               (const unsigned char *)d_pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
+        if (priors() && Ml > 0)
+            hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)d_pfix.p,
+                               (const T *)(d_scal.p + SC_LAMBDA), &ms->flag);
+        else if (Ml > 0)
+            hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
+                               (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), &ms->flag);
+        launch_pcg_blocks((T *)d_mc_M.p, (T *)c.y, (T *)c.z);
+        hipLaunchKernelGGL(k_mc_prec_inv, dim3((N + 255) / 256), dim3(256), 0, st, N, d_mc_M.p, c.cmask, &ms->flag);
+        ba_mc_dev h{};
+        HIPCHK(hipMemcpyAsync(&h, ms, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        return h.flag ? BA_ERR_SINGULAR : BA_OK;
+    }
+    // y = S v for the nine columns (FINAL: v = x) and the one-workgroup launch behind it (alpha; FINAL: |b - S x|^2)
+    template <bool FINAL> void mc_matvec(const McRun &c)
+    {
+        const ba_mc_dev *ms = d_mc.p;
+        const double *lam = (const double *)(d_scal.p + SC_LAMBDA);
+        if (Ml > 0)
+            hipLaunchKernelGGL((k_mc_point<FINAL>), dim3((unsigned)(((size_t)Ml * 8 + 255) / 256)), dim3(256), 0, st, Ml, (const int *)d_pt_ptr.p,
+                               (const int *)d_obs_cam.p, (const double *)d_rec.p, (const double *)d_dinv.p, (const double *)c.z, (const double *)c.p,
+                               (const double *)c.x, ms, d_mc_w.p);
+        if (sx.ndchunks > 0)
+            hipLaunchKernelGGL((k_mc_cam_chunks<FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, (const int *)d_dchunk_ptr.p,
+                               (const int *)d_cam_obs.p, (const int *)d_obs_pt.p, (const double *)d_rec.p, (const double *)d_mc_w.p, d_mc_slab.p, ms);
+        if (relposes())
+            hipLaunchKernelGGL((k_mc_cam<FINAL, true>), dim3(c.gm), dim3(256), 0, st, N, (const int *)d_cam_dchunk_ptr.p, (const double *)d_mc_slab.p,
+                               (const double *)d_V.p, lam, (const double *)c.z, (const double *)c.p, (const double *)c.x, (const double *)c.b,
+                               relpose_csr(), c.cmask, c.y, c.part_py, ms);
+        else
+            hipLaunchKernelGGL((k_mc_cam<FINAL, false>), dim3(c.gm), dim3(256), 0, st, N, (const int *)d_cam_dchunk_ptr.p, (const double *)d_mc_slab.p,
+                               (const double *)d_V.p, lam, (const double *)c.z, (const double *)c.p, (const double *)c.x, (const double *)c.b,
+                               ba_relpose_csr<double>{nullptr, nullptr, nullptr, nullptr}, c.cmask, c.y, c.part_py, ms);
+        hipLaunchKernelGGL((k_mc_alpha<FINAL>), dim3(1), dim3(256), 0, st, c.gm, (const double *)c.part_py, d_mc.p);
+    }
+    // One batch, its right-hand sides in c.b (`live` of them not zero): rounds of iterations with the state read back between them,
+    // then the product S X; the solution stays in c.x, the batch joins the statistics
+    int mc_solve_batch(McRun &c, int live)
+    {
+        ba_mc_dev *ms = d_mc.p;
+        ba_mc_dev h{};
+        hipLaunchKernelGGL(k_mc_init, dim3(c.gm), dim3(256), 0, st, N, (const double *)d_mc_M.p, (const double *)c.b, c.x, c.r, c.z, c.p, c.part_rz, c.part_rr);
+        hipLaunchKernelGGL((k_mc_scal<true>), dim3(1), dim3(256), 0, st, 0, c.gm, (const double *)c.part_rz, (const double *)c.part_rr, c.tol2, ms);
+        constexpr int ROUND = 16;
+        for (int k = 0; k < c.max_iter;) {
+            for (int e = std::min(c.max_iter, k + ROUND); k < e; k++) {
+                mc_matvec<false>(c);
+                hipLaunchKernelGGL(k_mc_update, dim3(c.gm), dim3(256), 0, st, N, (const double *)d_mc_M.p, (const double *)c.y, c.z, c.p, c.x, c.r, c.part_rz,
+                                   c.part_rr, (const ba_mc_dev *)ms);
+                hipLaunchKernelGGL((k_mc_scal<false>), dim3(1), dim3(256), 0, st, k, c.gm, (const double *)c.part_rz, (const double *)c.part_rr, c.tol2, ms);
+            }
+            HIPCHK(hipMemcpyAsync(&h, ms, sizeof h, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (h.alldone) break;
+        }
+        if (h.singular) return BA_ERR_SINGULAR;
+        mc_matvec<true>(c);
+        HIPCHK(hipMemcpyAsync(&h, ms, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        int bmax = 0;
+        for (int q = 0; q < BA_MC_NR; q++) {
+            if (!(h.bb[q] > 0)) continue;
+            bmax = std::max(bmax, h.iters[q]);
+            if (!h.done[q]) c.acc.unconverged++;
+            c.acc.worst_rel_residual = std::max(c.acc.worst_rel_residual, std::sqrt(h.res[q] / h.bb[q]));
+        }
+        c.acc.columns += live; c.acc.batches++; c.acc.total_iters += bmax;
+        c.acc.max_iters = std::max(c.acc.max_iters, bmax);
+        return BA_OK;
+    }
+    // Up to three points (ids, output slots): with_solve = their Y_p as one batch and the solve; then Sigma_pp out of c.x (a point nobody
+    // observes: I / lambda, no solve)
+    int mc_point_batch(McRun &c, const std::vector<int> &ids, const std::vector<int> &slots, bool with_solve, int *rq_pts, double *out_p)
+    {
+        const int np = (int)ids.size();
+        if (np == 0) return BA_OK;
+        int hreq[6] = {0, 0, 0, 0, 0, 0}, rc;
+        for (int i = 0; i < np; i++) { hreq[i] = ids[i]; hreq[3 + i] = slots[i]; }
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(rq_pts, hreq, sizeof hreq, hipMemcpyHostToDevice));
+        if (with_solve) {
+            HIPCHK(hipMemsetAsync(c.b, 0, sizeof(double) * (size_t)D * BA_MC_NR, st));
+            hipLaunchKernelGGL(k_mc_rhs_pts, dim3(1), dim3(64), 0, st, np, (const int *)rq_pts, Ml, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
+                               (const double *)d_rec.p, (const double *)d_dinv.p, (const double *)d_tri.p, c.pfix, c.b);
+            if ((rc = mc_solve_batch(c, 3 * np))) return rc;
+        }
+        hipLaunchKernelGGL(k_mc_get_pts, dim3(1), dim3(64), 0, st, np, (const int *)rq_pts, (const int *)(rq_pts + 3), Ml, (const int *)d_pt_ptr.p,
+                           (const int *)d_obs_cam.p, (const double *)d_rec.p, (const double *)d_dinv.p, (const double *)d_tri.p, c.pfix,
+                           (const double *)(d_scal.p + SC_LAMBDA), (const double *)c.x, out_p);
+        return BA_OK;
+    }
+
+    int cov_pcg(double lambda, int max_iter, double rel_tol, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids,
+                double *pt_cov, ba_cov_pcg_stats *stats) override
+    {
+        if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG;
+        else {
+            // refusals: host side, before any launch
+            if (!iterative() || sharded() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
+                !(rel_tol >= 0 && rel_tol < 1) || n_pairs < 0 || n_pts < 0 || (n_pairs > 0 && (!cam_pairs || !cam_cov)) ||
+                (n_pts > 0 && (!pt_ids || !pt_cov)))
+                return BA_ERR_ARG;
+            for (int q = 0; q < 2 * n_pairs; q++)
+                if (cam_pairs[q] < 0 || cam_pairs[q] >= N) return BA_ERR_ARG;
+            for (int q = 0; q < n_pts; q++)
+                if (pt_ids[q] < 0 || pt_ids[q] >= Ml) return BA_ERR_ARG;
+            int rc;
+            McRun c;
+            if ((rc = mc_begin(max_iter ? max_iter : pcg_max_iter, rel_tol != 0 ? rel_tol : pcg_rel_tol, c))) return rc;
+            // the mask on the host: which columns are live, which requests need no launch
+            std::vector<unsigned short> hcm((size_t)N, 0);
+            std::vector<unsigned char> hpf((size_t)(Ml > 0 ? Ml : 1), 0);
+            HIPCHK(hipStreamSynchronize(st));
+            if (masked && d_cmask.p) HIPCHK(hipMemcpy(hcm.data(), d_cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
+            if (masked && d_pfix.p && Ml > 0) HIPCHK(hipMemcpy(hpf.data(), d_pfix.p, (size_t)Ml, hipMemcpyDeviceToHost));
+            DevBuf<int> d_req; // pairs [2 n_pairs] | order [n_pairs] | point batch: ids [3], slots [3]
+            DevBuf<double> d_out;
+            if ((rc = d_req.alloc((size_t)3 * n_pairs + 6)) || (rc = d_out.alloc((size_t)81 * n_pairs + (size_t)9 * n_pts + 1))) { (void)hipGetLastError(); return rc; }
+            int *rq_pairs = d_req.p, *rq_order = rq_pairs + 2 * (size_t)n_pairs, *rq_pts = rq_order + n_pairs;
+            double *out_c = d_out.p, *out_p = out_c + (size_t)81 * n_pairs;
+            // camera pairs by column block max(a, b), a block's pairs in request order
+            std::vector<int> order((size_t)n_pairs);
+            std::iota(order.begin(), order.end(), 0);
+            auto blk = [&](int q) { return std::max(cam_pairs[2 * q], cam_pairs[2 * q + 1]); };
+            std::stable_sort(order.begin(), order.end(), [&](int u, int v) { return blk(u) < blk(v); });
+            if (n_pairs > 0) {
+                HIPCHK(hipMemcpy(rq_pairs, cam_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(rq_order, order.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice));
+            }
+            HIPCHK(hipMemsetAsync(d_out.p, 0, sizeof(double) * d_out.n, st)); // (a fully fixed camera or a fixed point: zeros, no launch)
+            if ((rc = mc_prepare(lambda, c))) return rc;
+            // camera column blocks
+            for (int lo = 0; lo < n_pairs;) {
+                int hi = lo;
+                const int b = blk(order[lo]);
+                while (hi < n_pairs && blk(order[hi]) == b) hi++;
+                int live = 0;
+                for (int q = 0; q < 9; q++) live += !((hcm[b] >> q) & 1);
+                if (live > 0) {
+                    HIPCHK(hipMemsetAsync(c.b, 0, sizeof(double) * (size_t)D * BA_MC_NR, st));
+                    hipLaunchKernelGGL(k_mc_rhs_cam, dim3(1), dim3(64), 0, st, b, c.cmask, c.b);
+                    if ((rc = mc_solve_batch(c, live))) return rc;
+                    hipLaunchKernelGGL(k_mc_get_cams, dim3((unsigned)(((size_t)(hi - lo) * 81 + 255) / 256)), dim3(256), 0, st, hi - lo, (const int *)(rq_order + lo),
+                                       (const int *)rq_pairs, b, (const double *)c.x, c.cmask, out_c);
+                }
+                lo = hi;
+            }
+            // points, three to a batch: first the ones that need a solve (free, observed), in request order; then the ones nobody
+            // observes (I / lambda; lambda = 0 never gets here: the point check has refused).  A fixed point's zeros are in place.
+            for (int pass = 0; pass < 2; pass++) {
+                std::vector<int> ids, slots;
+                for (int q = 0; q < n_pts; q++) {
+                    const int j = pt_ids[q];
+                    if (hpf[j] || (sx.pt_ptr[j] == sx.pt_ptr[j + 1]) != (pass == 1)) continue;
+                    ids.push_back(j); slots.push_back(q);
+                    if (ids.size() == 3) {
+                        if ((rc = mc_point_batch(c, ids, slots, pass == 0, rq_pts, out_p))) return rc;
+                        ids.clear(); slots.clear();
+                    }
+                }
+                if ((rc = mc_point_batch(c, ids, slots, pass == 0, rq_pts, out_p))) return rc;
+            }
+            HIPCHK(hipEventRecord(ev[EV_T1], st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            if (n_pairs > 0) HIPCHK(hipMemcpy(cam_cov, out_c, sizeof(double) * 81 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+            if (n_pts > 0) HIPCHK(hipMemcpy(pt_cov, out_p, sizeof(double) * 9 * (size_t)n_pts, hipMemcpyDeviceToHost));
+            c.acc.ms = ev_ms(EV_T0, EV_T1);
+            if (stats) *stats = c.acc;
+            return BA_OK;
+        }
     }
 
     int set_lambda(T lambda)
@@ -2542,6 +2773,11 @@ int ba_solver_covariance_compute(ba_solver *s, double lambda) { return !s ? BA_E
 int ba_solver_covariance_get(ba_solver *s, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts, const int *pt_ids, double *pt_cov)
 {
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->cov_get(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov);
+}
+int ba_solver_covariance_pcg(ba_solver *s, double lambda, int max_iter, double rel_tol, int n_pairs, const int *cam_pairs, double *cam_cov, int n_pts,
+                             const int *pt_ids, double *pt_cov, ba_cov_pcg_stats *stats)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->cov_pcg(lambda, max_iter, rel_tol, n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov, stats);
 }
 int ba_solver_covariance_timing(ba_solver *s, double *ms4) { return !(s && ms4) ? BA_ERR_ARG : s->impl->cov_timing(ms4); }
 

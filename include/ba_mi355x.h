@@ -349,6 +349,50 @@ int ba_solver_covariance_get(ba_solver *s, int n_pairs, const int *cam_pairs, do
  * the point kernel of the last ba_solver_covariance_get that asked for points. */
 int ba_solver_covariance_timing(ba_solver *s, double *ms4);
 
+/* ---- covariance blocks of BA_ITERSCHUR: matrix-free, by a multi-column PCG ---------------------------------- */
+
+/* The contract of ba_solver_covariance_compute / _get above -- blocks of Sigma = (J'J + lambda I)^-1 on the free parameters at the last
+ * ba_solver_linearize, exactly 0 in the rows and columns of fixed parameters, the order of BA_GET_DX -- for the one kind that never
+ * forms S, solved inexactly and in one call.  Sigma_cc = S^-1, so Sigma_ab is rows a of the solution of S X = E_b (9 columns), and
+ * Sigma_pp = U_p^-1 + Y_p' S^-1 Y_p with Y_p = W_p U_p^-1 (3 columns).  The columns are solved nine at a time by preconditioned conjugate
+ * gradients whose product by S reads every elimination record once for all nine (csrc/ba_pcg_multi.hip.h).
+ * Right-hand sides: a pair (a, b) is served from column block max(a, b), so Sigma_ab and Sigma_ba of one call are each other's transpose
+ * bit for bit; pairs with the same column block share one solve; a diagonal block and a point block are returned symmetrised,
+ * (X + X') / 2; points are packed three to a batch; the column of a fixed parameter is not solved (a fully fixed camera or a fixed point:
+ * zeros without a launch); a point nobody observes returns I / lambda, or BA_ERR_SINGULAR at lambda = 0.  Every sum has a fixed order that
+ * involves the column's own data only, and there are no atomics: a block's bits do not depend on what else is in the request.
+ * Operator: S(lambda) of the current linearisation (the elimination is run again at this lambda; priors are in V and U0, the relative-pose
+ * blocks H_ab are applied per column); the row of a fixed parameter is the identity.  Preconditioner: block Jacobi at this lambda, B_a
+ * inverted in fp64, whatever ba_solver_set_preconditioner holds (that setting is left alone).
+ * max_iter = 0 / rel_tol = 0: the values of ba_solver_set_pcg.  A column stops at |r_k| <= rel_tol |b| (the recurrence's residual, as in a
+ * trial's solve) or at max_iter.  A column that ends at the cap is no error: BA_OK, and stats->unconverged counts such columns.
+ * Accuracy per column: |x - S^-1 b|_2 <= |S^-1|_2 |b - S x|_2, and stats->worst_rel_residual is the largest |b - S x| / |b| (|b| = 1 for a
+ * camera column), from one more product by S behind each batch.
+ * BA_ERR_SINGULAR (device flags read back with the call; the output arrays are then unspecified): a pivot <= 0 of a free point's 3 x 3
+ * block, a B_a that is not positive definite (the trial's fallback to the block's diagonal would hide a rank defect), p'Sp <= 0 or not
+ * finite for a live column.  NOT detected: an S that is merely semidefinite (lambda = 0 without a gauge) whose Krylov spaces never show
+ * it -- such a solve ends as `unconverged` with a large residual, so look at the stats.
+ * BA_ERR_ARG, decided on the host before any launch, the solver unchanged: a kind other than BA_ITERSCHUR, BA_F32, no ba_solver_linearize
+ * since creation / ba_solver_set_state / ba_minimize, a mask or a measurement model set since the last linearisation, lambda < 0 or not
+ * finite, max_iter < 0, rel_tol outside [0, 1), an index out of range, a negative count, a NULL array with a positive count.
+ * The LM state is untouched, as with ba_solver_covariance_compute: a ba_solver_try_step or ba_minimize behind the call returns the bits it
+ * returns without it; behind a ba_solver_try_step, BA_GET_DX, BA_GET_RHS, xTest and ba_solver_accept are what they were, and
+ * ba_solver_pcg_stats does not count these solves.  What the call spends are the last trial's elimination records (the fused
+ * linearisation's pre-made ones included) and scratch every trial rebuilds.
+ * Memory: work vectors of its own, allocated by the first call, counted by ba_solver_device_bytes, released by ba_solver_free:
+ *   8 (6 * 81 N + 27 max(M, 1) + 81 max(chunks, 1) + 81 N + 27 ceil(N / 28)) + sizeof(state) bytes
+ * (x, r, z, p, S p and the right-hand sides at 9 columns x 9 N; the point pass; the slab of the camera chunks of <= 32 observations;
+ * B_a^-1; three lists of workgroup partials), plus 12 n_pairs + 24 + 8 (81 n_pairs + 9 n_pts + 1) bytes for the length of the call.
+ * BA_ERR_NOMEM when they do not fit; the solver stays usable. */
+typedef struct {
+    long long columns, batches, total_iters; /* live right-hand sides solved; 9-column batches; sum over batches of the batch's iterations */
+    int max_iters, unconverged;              /* slowest column; columns that ended at the cap */
+    double worst_rel_residual;               /* max over columns of |b - S x| / |b|, from one more product by S behind each batch */
+    double ms;                               /* device ms of the call (HIP events) */
+} ba_cov_pcg_stats;
+int ba_solver_covariance_pcg(ba_solver *s, double lambda, int max_iter, double rel_tol, int n_pairs, const int *cam_pairs, double *cam_cov,
+                             int n_pts, const int *pt_ids, double *pt_cov, ba_cov_pcg_stats *stats /* may be NULL */);
+
 /* ---- measurement model (no reference counterpart beyond its psi; Ceres' LossFunction, g2o's robust kernels and information) ---------- */
 
 /* With r_o = w_o (pi(cam, pt) - meas_o) the weighted reprojection residual of observation o in pixels (w_o = 1 without weights) and

@@ -46,6 +46,7 @@ EXPORTS = [
     "ba_solver_set_point_priors", "ba_solver_set_centre_priors", "ba_solver_set_intrinsics_priors", "ba_solver_prior_energy",
     "ba_solver_set_relative_poses", "ba_solver_relative_pose_energy",
     "ba_solver_set_preconditioner", "ba_solver_preconditioner_info", "ba_relpose_forest_plan", "ba_problem_covisibility",
+    "ba_intrinsics_group_plan", "ba_solver_set_shared_intrinsics", "ba_solver_shared_intrinsics_info",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -159,6 +160,9 @@ def lib():
         L.ba_solver_preconditioner_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_relpose_forest_plan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         L.ba_problem_covisibility.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_intrinsics_group_plan.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.ba_solver_set_shared_intrinsics.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_shared_intrinsics_info.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_problem_dims.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.ba_problem_get.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.ba_problem_load_bal.argtypes = [C.c_char_p, C.c_void_p]
@@ -380,6 +384,25 @@ class Solver:
         d["fallback_trees"] = int(fb.value)
         return d
 
+    def set_shared_intrinsics(self, group_of=None):
+        """ITERSCHUR: the cameras with one label >= 0 in group_of (N ints; < 0: a camera of its own) solve for one f, k1, k2 from the next
+        try_step() / minimize() on.  Their f, k1, k2 must be bit-equal in the resident state (set_state) and their FIX_INTRINSICS bits the
+        same.  None, all negative or no label used twice: no groups."""
+        if group_of is not None:
+            group_of = np.asarray(group_of)
+            if group_of.shape != (self.problem.N,) or group_of.dtype.kind not in "iu":
+                raise ValueError("group_of must be an integer array of shape (%d,), got %s %s" % (self.problem.N, group_of.dtype, group_of.shape))
+            if group_of.size and (group_of.min() < -2 ** 31 or group_of.max() >= 2 ** 31):
+                raise ValueError("group_of: a label does not fit a C int")
+            group_of = np.ascontiguousarray(group_of, np.int32)
+        _chk(lib().ba_solver_set_shared_intrinsics(self._h, _p(group_of)), "ba_solver_set_shared_intrinsics")
+
+    def shared_intrinsics_info(self):
+        """dict(groups, grouped, largest_group, chunks) of the groups in force."""
+        out = np.zeros(4, np.int64)
+        _chk(lib().ba_solver_shared_intrinsics_info(self._h, _p(out)), "ba_solver_shared_intrinsics_info")
+        return dict(zip(("groups", "grouped", "largest_group", "chunks"), (int(v) for v in out)))
+
     def set_constant(self, cam_mask=None, pt_fixed=None):
         """Hold parameters constant from the next linearize() / minimize() on: cam_mask uint16[N] (FIX_* bits), pt_fixed bool / uint8[M]
         of the problem (None: nothing of that kind; both None or all zero: the unmasked solver)."""
@@ -578,6 +601,27 @@ def forest_plan(N, pairs, max_tree):
     kept = np.zeros(n, np.uint8)
     _chk(lib().ba_relpose_forest_plan(int(N), n, _p(pairs), int(max_tree), _p(parent), _p(via), _p(order), _p(kept)), "ba_relpose_forest_plan")
     return dict(parent=parent, via=via, order=order, kept=kept.astype(bool))
+
+
+def intrinsics_group_plan(N, group_of, chunk=256):
+    """ba_intrinsics_group_plan (host only): dict(group_ptr [g + 1], members, chunk_ptr [c + 1], chunk_group [c]) of the groups that
+    Solver.set_shared_intrinsics builds from the labels group_of ([N]; < 0: no group) with at most `chunk` members per chunk."""
+    if group_of is not None:
+        group_of = np.asarray(group_of)
+        if int(N) >= 0 and (group_of.shape != (int(N),) or (group_of.size and group_of.dtype.kind not in "iu")):  # (N < 0: refused unread)
+            raise ValueError("group_of must be an integer array of shape (%d,), got %s %s" % (int(N), group_of.dtype, group_of.shape))
+        if group_of.size and (group_of.min() < -2 ** 31 or group_of.max() >= 2 ** 31):
+            raise ValueError("group_of: a label does not fit a C int")
+        group_of = np.ascontiguousarray(group_of.reshape(-1), np.int32)
+    ng, nc = C.c_int(0), C.c_int(0)
+    _chk(lib().ba_intrinsics_group_plan(int(N), _p(group_of), int(chunk), C.byref(ng), None, None, C.byref(nc), None, None),
+         "ba_intrinsics_group_plan")
+    n = max(int(N), 0)
+    group_ptr, members = np.zeros(ng.value + 1, np.int32), np.zeros(n, np.int32)
+    chunk_ptr, chunk_group = np.zeros(nc.value + 1, np.int32), np.zeros(nc.value, np.int32)
+    _chk(lib().ba_intrinsics_group_plan(int(N), _p(group_of), int(chunk), C.byref(ng), _p(group_ptr), _p(members), C.byref(nc), _p(chunk_ptr),
+                                        _p(chunk_group)), "ba_intrinsics_group_plan")
+    return dict(group_ptr=group_ptr, members=members[:group_ptr[-1]].copy(), chunk_ptr=chunk_ptr, chunk_group=chunk_group)
 
 
 def relative_pose(cam15, a, b):

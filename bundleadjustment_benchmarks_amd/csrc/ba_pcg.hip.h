@@ -26,6 +26,11 @@
 // launched behind k_pcg_prec_inv and behind every k_pcg_update, which leave those cameras' z and r'z alone (FOREST instantiations).  The
 // trees' partials of r'z follow the gc per-camera ones, so the list of r'z has gz = gc + trees entries per slot (gz = gc without a
 // forest) while |r|^2 keeps gc.  BA_PRECOND_VISIBILITY_FOREST is the same with one partial per 256 trees (k_pcg_forest_rz).
+//
+// Shared intrinsics (ba_pcg_share.hip.h): with groups of cameras that solve for one f, k1, k2 the projection Pi (rows 6..8 of a group's
+// members <- their mean) is launched on rhs in front of k_pcg_prec_inv and on z_0 behind it, on y = S p behind k_pcg_cam /
+// k_pcg_relpose, on z behind k_pcg_update (behind the forest's apply), and the partials of |rhs - y|^2 are formed again from the
+// projected y; the kernels of this file do not know about it.
 #ifndef BA_PCG_HIP_H
 #define BA_PCG_HIP_H
 

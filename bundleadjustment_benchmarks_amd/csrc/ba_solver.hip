@@ -13,6 +13,7 @@
 #include "ba_pcg.hip.h"
 #include "ba_cov.hip.h"
 #include "ba_pcg_multi.hip.h"
+#include "ba_pcg_share.hip.h"
 #include "ba_prior.hip.h"
 #include "ba_relpose.hip.h"
 
@@ -99,6 +100,8 @@ struct SolverBase {
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
     virtual int set_precond(int kind, int max_tree) = 0;
     virtual int precond_info(long long *out6, int *fallback_trees) = 0;
+    virtual int set_shared(const int *group_of) = 0;
+    virtual int shared_info(long long *out4) = 0;
     virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
     virtual int set_loss(int kind, double scale) = 0;
     virtual int set_obs_weights(const double *w) = 0;
@@ -1118,6 +1121,120 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
 
+    // ---- shared intrinsics (ba_solver_set_shared_intrinsics; ba_pcg_share.hip.h) -------------------------------
+    // The lists of ba_intrinsics_group_plan with chunks of BA_SHARE_CHUNK members, laid into chunk slots, 8 to a workgroup of
+    // k_pcg_share: a group of 2 .. BA_SHARE_LOCAL chunks never crosses a workgroup (empty slots in front of it where it would).
+    // Without a group there is no buffer and not one launch differs from a solver that never had one.
+    struct Share {
+        int ngroups = 0, ngrouped = 0, largest = 0, nchunks = 0, nslots = 0, nwide = 0;
+        DevBuf<ba_share_chunk> desc; // [nslots]
+        DevBuf<int> members, wide;   // [ngrouped]; [nwide]: the slots of groups of more than BA_SHARE_LOCAL chunks
+        DevBuf<double> part;         // [nslots][3]
+        std::vector<int> h_gptr, h_members; // host copy: the refusals of set_state / set_constant
+        void swap(Share &o)
+        {
+            std::swap(ngroups, o.ngroups); std::swap(ngrouped, o.ngrouped); std::swap(largest, o.largest); std::swap(nchunks, o.nchunks);
+            std::swap(nslots, o.nslots); std::swap(nwide, o.nwide);
+            std::swap(desc.p, o.desc.p); std::swap(desc.n, o.desc.n); std::swap(members.p, o.members.p); std::swap(members.n, o.members.n);
+            std::swap(wide.p, o.wide.p); std::swap(wide.n, o.wide.n); std::swap(part.p, o.part.p); std::swap(part.n, o.part.n);
+            h_gptr.swap(o.h_gptr); h_members.swap(o.h_members);
+        }
+        size_t bytes() const { return bytes_of(desc) + bytes_of(members) + bytes_of(wide) + bytes_of(part); }
+    } sh;
+    bool share_on() const { return sh.ngroups > 0; }
+    // v <- Pi v.  CHECK: a launch of the iteration, which returns at once behind convergence
+    template <bool CHECK> void launch_share(T *v)
+    {
+        hipLaunchKernelGGL((k_pcg_share<T, CHECK>), dim3((sh.nslots + 7) / 8), dim3(256), 0, st, sh.nslots, (const ba_share_chunk *)sh.desc.p,
+                           (const int *)sh.members.p, v, sh.part.p, (const ba_pcg_dev *)d_pcg.p);
+        if (sh.nwide > 0)
+            hipLaunchKernelGGL((k_pcg_share_wide<T, CHECK>), dim3((sh.nwide + 7) / 8), dim3(256), 0, st, sh.nwide, (const int *)sh.wide.p,
+                               (const ba_share_chunk *)sh.desc.p, (const int *)sh.members.p, v, (const double *)sh.part.p, (const ba_pcg_dev *)d_pcg.p);
+    }
+    // true when the members of every group of (gptr, members) hold the same bits in f, k1, k2 of cam (SoA [15][N], rows 12..14)
+    static bool share_equal(const std::vector<int> &gptr, const std::vector<int> &members, const T *cam, int N)
+    {
+        for (size_t g = 0; g + 1 < gptr.size(); g++)
+            for (int m = gptr[g] + 1; m < gptr[g + 1]; m++)
+                for (int q = 12; q < 15; q++)
+                    if (std::memcmp(cam + (size_t)q * N + members[m], cam + (size_t)q * N + members[gptr[g]], sizeof(T)) != 0) return false;
+        return true;
+    }
+    // ... and the same bits 6..8 of a camera mask (nullptr: no mask)
+    static bool share_mask_uniform(const std::vector<int> &gptr, const std::vector<int> &members, const unsigned short *cm)
+    {
+        for (size_t g = 0; cm && g + 1 < gptr.size(); g++)
+            for (int m = gptr[g] + 1; m < gptr[g + 1]; m++)
+                if ((cm[members[m]] & BA_FIX_INTRINSICS) != (cm[members[gptr[g]]] & BA_FIX_INTRINSICS)) return false;
+        return true;
+    }
+    int set_shared(const int *group_of) override
+    {
+        try {
+            return set_shared_impl(group_of);
+        } catch (const std::bad_alloc &) { // (the host lists; nothing of the solver has been touched yet)
+            return BA_ERR_NOMEM;
+        }
+    }
+    int set_shared_impl(const int *group_of)
+    {
+        if (!iterative()) return BA_ERR_ARG;
+        Share ns;
+        int rc;
+        if (group_of) {
+            std::vector<int> gptr((size_t)N / 2 + 2), members((size_t)N + 1), cptr((size_t)N + 2), cgrp((size_t)N + 1);
+            if ((rc = ba_intrinsics_group_plan(N, group_of, BA_SHARE_CHUNK, &ns.ngroups, gptr.data(), members.data(), &ns.nchunks, cptr.data(), cgrp.data())))
+                return rc;
+            gptr.resize((size_t)ns.ngroups + 1);
+            ns.ngrouped = gptr[ns.ngroups];
+            members.resize((size_t)ns.ngrouped);
+            if (ns.ngroups > 0) {
+                // refusals: the members' f, k1, k2 in the resident state, their mask bits 6..8
+                std::vector<T> hc;
+                if ((rc = dl(d_cam[0].p, 15 * (size_t)N, hc))) return rc;
+                if (!share_equal(gptr, members, hc.data(), N)) return BA_ERR_ARG;
+                if (masked && d_cmask.p) {
+                    std::vector<unsigned short> hm((size_t)N);
+                    HIPCHK(hipMemcpy(hm.data(), d_cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
+                    if (!share_mask_uniform(gptr, members, hm.data())) return BA_ERR_ARG;
+                }
+                std::vector<ba_share_chunk> desc;
+                std::vector<int> wide;
+                for (int g = 0, c = 0; g < ns.ngroups; g++) {
+                    int nc = 0;
+                    while (c + nc < ns.nchunks && cgrp[c + nc] == g) nc++;
+                    if (nc > 1 && nc <= BA_SHARE_LOCAL)
+                        while (desc.size() % 8 + (size_t)nc > 8) desc.push_back(ba_share_chunk{0, 0, 0, 1, 1}); // (an empty slot)
+                    const int c0 = (int)desc.size(), ng = gptr[g + 1] - gptr[g];
+                    for (int k = 0; k < nc; k++) {
+                        if (nc > BA_SHARE_LOCAL) wide.push_back((int)desc.size());
+                        desc.push_back(ba_share_chunk{cptr[c + k], cptr[c + k + 1] - cptr[c + k], c0, nc, ng});
+                    }
+                    ns.largest = std::max(ns.largest, ng);
+                    c += nc;
+                }
+                ns.nslots = (int)desc.size();
+                ns.nwide = (int)wide.size();
+                if ((rc = ns.desc.upload(desc)) || (rc = ns.members.upload(members)) || (rc = ns.wide.upload(wide)) ||
+                    (rc = ns.part.alloc((size_t)3 * ns.nslots))) { (void)hipGetLastError(); return rc; }
+                HIPCHK(hipMemset(ns.part.p, 0, sizeof(double) * ns.part.n));
+                ns.h_gptr.swap(gptr); ns.h_members.swap(members);
+            }
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        sh.swap(ns);
+        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl}) // (captured with the old launch sequence)
+            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        have_step = false; // (xTest is the step of the other group set: its members' f, k1, k2 need not be equal)
+        return BA_OK;
+    }
+    int shared_info(long long *out4) override
+    {
+        if (!iterative() || !out4) return BA_ERR_ARG;
+        out4[0] = sh.ngroups; out4[1] = sh.ngrouped; out4[2] = sh.largest; out4[3] = sh.nchunks;
+        return BA_OK;
+    }
+
     // segment A behind k_elim_chol: block-Jacobi preconditioner, reduced rhs, g_c for the retraction's rho terms, x_0 = 0 and the
     // recurrence's start (p_{-1} = 0, z_0, slot-0 partials, |rhs|^2)
     // (Bm, rhs, gc_out: the trial's own buffers unless ba_solver_covariance_pcg hands in its scratch)
@@ -1132,6 +1249,7 @@ template <typename T> struct Solver final : SolverBase {
     void launch_pcg_prep()
     {
         launch_pcg_blocks();
+        if (share_on()) launch_share<false>(d_pcg_b.p); // rhs <- Pi rhs: r_0, |rhs|^2 and z_0 see it (BA_GET_RHS returns it)
         if (forest_on()) { // the factor reads B_a in front of its inversion in place; z_0 and r_0'z_0 of the trees behind it
             if (fo.width == 9) launch_forest_edges(); // (behind the elimination's and the constraints' records)
             launch_forest_factor();
@@ -1141,6 +1259,7 @@ template <typename T> struct Solver final : SolverBase {
         } else
             hipLaunchKernelGGL((k_pcg_prec_inv<T>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
                                pcg_part_rz(), pcg_part_rr(), (const unsigned char *)nullptr);
+        if (share_on()) launch_share<false>(d_pcg_z.p); // z_0 <- Pi z_0 (r_0'z_0 of the unprojected z_0 is r_0'(Pi z_0): r_0 is in range(Pi))
         hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(256), 0, st, pcg_part_rr(), pcg_gc, d_pcg.p);
     }
     // y = S v: the point pass, then the camera pass (chunk partials in d_dslab, then per camera)
@@ -1159,6 +1278,11 @@ template <typename T> struct Solver final : SolverBase {
             hipLaunchKernelGGL((k_pcg_relpose<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, relpose_csr(), (const T *)d_pcg_z.p, (const T *)d_pcg_p.p,
                                (const T *)d_dxc.p, (const T *)d_pcg_b.p, (const double *)pcg_part_rz(), pcg_gz(), d_pcg_y.p,
                                FINAL ? pcg_part_res() : pcg_part_py(), (const ba_pcg_dev *)d_pcg.p);
+        if (share_on()) { // y <- Pi y (p'y of the unprojected y is p'(Pi y)); FINAL: |Pi (rhs - S x)|^2 from the projected y
+            launch_share<!FINAL>(d_pcg_y.p);
+            if (FINAL)
+                hipLaunchKernelGGL((k_pcg_share_res<T>), dim3(pcg_gq), dim3(256), 0, st, N, (const T *)d_pcg_b.p, (const T *)d_pcg_y.p, pcg_part_res());
+        }
     }
     // segment B's solve: pcg_max_iter iterations of four launches (the ones behind convergence return at once), the product S x of the
     // step and the statistics.  The solution is d_dxc, where launch_backsub_retract reads it.
@@ -1175,6 +1299,7 @@ template <typename T> struct Solver final : SolverBase {
             } else
                 hipLaunchKernelGGL((k_pcg_update<T>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, d_pcg_r.p,
                                    pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p, (const unsigned char *)nullptr);
+            if (share_on()) launch_share<true>(d_pcg_z.p); // z_{k+1} <- Pi z_{k+1}, behind whatever produced it
         }
         launch_pcg_matvec<true>(pcg_max_iter, tol2);
         // (a trial ba_minimize enqueued behind the row that ended the run is not counted: lm->stop is already set when it runs)
@@ -1218,7 +1343,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes();
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1512,7 +1637,7 @@ template <typename T> struct Solver final : SolverBase {
         if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG;
         else {
             // refusals: host side, before any launch
-            if (!iterative() || sharded() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
+            if (!iterative() || sharded() || share_on() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
                 !(rel_tol >= 0 && rel_tol < 1) || n_pairs < 0 || n_pts < 0 || (n_pairs > 0 && (!cam_pairs || !cam_cov)) ||
                 (n_pts > 0 && (!pt_ids || !pt_cov)))
                 return BA_ERR_ARG;
@@ -1640,6 +1765,7 @@ template <typename T> struct Solver final : SolverBase {
         }
         if (!pf) all = all && sx.M == 0;
         if (any && all) return BA_ERR_ARG; // nothing left to optimise
+        if (share_on() && !share_mask_uniform(sh.h_gptr, sh.h_members, cm)) return BA_ERR_ARG; // (a shared parameter is fixed for all or for none)
         HIPCHK(hipStreamSynchronize(st));
         cov_valid = false;
         if (!any) { d_cmask.release(); d_pfix.release(); }
@@ -2230,20 +2356,19 @@ template <typename T> struct Solver final : SolverBase {
 
     int set_state(const double *cam15, const double *pts) override
     {
+        std::vector<T> h((size_t)(cam15 ? 15 : 0) * N);
+        for (int a = 0; cam15 && a < N; a++)
+            for (int q = 0; q < 15; q++) h[(size_t)q * N + a] = (T)cam15[15 * (size_t)a + q];
+        if (cam15 && share_on() && !share_equal(sh.h_gptr, sh.h_members, h.data(), N)) return BA_ERR_ARG; // (state unchanged)
         HIPCHK(hipStreamSynchronize(st));
         cov_valid = false;
         have_lin = false; // (J is another state's)
-        if (cam15) {
-            std::vector<T> h((size_t)15 * N);
-            for (int a = 0; a < N; a++)
-                for (int q = 0; q < 15; q++) h[(size_t)q * N + a] = (T)cam15[15 * (size_t)a + q];
-            HIPCHK(hipMemcpy(d_cam[0].p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-        }
+        if (cam15) HIPCHK(hipMemcpy(d_cam[0].p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
         if (pts && Ml > 0) {
-            std::vector<T> h((size_t)3 * Ml);
+            std::vector<T> hp((size_t)3 * Ml);
             for (int j = 0; j < Ml; j++)
-                for (int q = 0; q < 3; q++) h[(size_t)q * Ml + j] = (T)pts[3 * (size_t)j + q];
-            HIPCHK(hipMemcpy(d_pts[0].p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+                for (int q = 0; q < 3; q++) hp[(size_t)q * Ml + j] = (T)pts[3 * (size_t)j + q];
+            HIPCHK(hipMemcpy(d_pts[0].p, hp.data(), sizeof(T) * hp.size(), hipMemcpyHostToDevice));
         }
         have_step = false;
         return BA_OK;
@@ -2762,6 +2887,8 @@ int ba_solver_preconditioner_info(ba_solver *s, long long *out6, int *fallback_t
 {
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->precond_info(out6, fallback_trees);
 }
+int ba_solver_set_shared_intrinsics(ba_solver *s, const int *group_of) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_shared(group_of); }
+int ba_solver_shared_intrinsics_info(ba_solver *s, long long *out4) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->shared_info(out4); }
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

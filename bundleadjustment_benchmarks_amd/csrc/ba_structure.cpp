@@ -218,6 +218,49 @@ extern "C" int ba_relpose_forest_plan(int N, int n, const int *cam_pairs, int ma
     return BA_OK;
 }
 
+// The groups and chunks behind ba_solver_set_shared_intrinsics (ba_mi355x.h states the rule; the solver builds its device lists from
+// these arrays, tests/shared_checks.py restates it).
+extern "C" int ba_intrinsics_group_plan(int N, const int *group_of, int chunk, int *n_groups, int *group_ptr, int *members, int *n_chunks,
+                                        int *chunk_ptr, int *chunk_group)
+{
+    if (N < 0 || (N > 0 && !group_of) || chunk < 1) return BA_ERR_ARG;
+    try {
+        // cameras by (label, index); a run of one label with two or more cameras is a group, the groups then by their lowest member
+        std::vector<int> by((size_t)0);
+        for (int a = 0; a < N; a++)
+            if (group_of[a] >= 0) by.push_back(a);
+        std::stable_sort(by.begin(), by.end(), [&](int u, int v) { return group_of[u] < group_of[v]; });
+        std::vector<std::pair<int, int>> runs; // (first position in `by`, length), lowest member first inside a run
+        for (size_t i = 0; i < by.size();) {
+            size_t j = i;
+            while (j < by.size() && group_of[by[j]] == group_of[by[i]]) j++;
+            if (j - i >= 2) runs.emplace_back((int)i, (int)(j - i));
+            i = j;
+        }
+        std::sort(runs.begin(), runs.end(), [&](const std::pair<int, int> &u, const std::pair<int, int> &v) { return by[u.first] < by[v.first]; });
+        int ng = 0, nm = 0, nc = 0;
+        for (const auto &r : runs) {
+            if (group_ptr) group_ptr[ng] = nm;
+            for (int k = 0; k < r.second; k += chunk) {
+                if (chunk_ptr) chunk_ptr[nc] = nm + k;
+                if (chunk_group) chunk_group[nc] = ng;
+                nc++;
+            }
+            for (int k = 0; k < r.second; k++)
+                if (members) members[nm + k] = by[(size_t)r.first + k];
+            nm += r.second;
+            ng++;
+        }
+        if (group_ptr) group_ptr[ng] = nm;
+        if (chunk_ptr) chunk_ptr[nc] = nm;
+        if (n_groups) *n_groups = ng;
+        if (n_chunks) *n_chunks = nc;
+    } catch (const std::bad_alloc &) {
+        return BA_ERR_NOMEM;
+    }
+    return BA_OK;
+}
+
 // The co-visibility graph behind BA_PRECOND_VISIBILITY_FOREST (ba_mi355x.h states the rule, tests/visibility_checks.py restates it).
 // Counts: dense N x N up to 2048 cameras; beyond that packed keys a N + b, sorted and run-length counted whenever 16 M of them have
 // gathered, the runs merged into the sorted list so far -- memory follows the number of distinct pairs, not the number of points.

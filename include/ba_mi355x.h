@@ -534,6 +534,48 @@ int ba_relpose_forest_plan(int N, int n, const int *cam_pairs, int max_tree, int
 #define BA_VIS_TRACK_MAX_DEFAULT 64
 int ba_problem_covisibility(const ba_problem *p, int track_max, long long *n_pairs, int *pairs, int *weight);
 
+/* ---- shared intrinsics for BA_ITERSCHUR (no reference counterpart; Ceres' one intrinsics parameter block handed to many residual
+ * blocks): one physical camera behind many frames, the heads of a rig ------------------------------------ */
+
+/* Host only (no GPU): the groups and chunks ba_solver_set_shared_intrinsics builds from one label per camera.  group_of[a] < 0: camera a
+ * keeps its own intrinsics; equal labels >= 0 form a group; a label used once is no group.  Groups are numbered by their lowest member,
+ * a group's members ascend; chunks hold at most `chunk` members (>= 1; the solver uses 256), never span groups and run in group order.
+ *   *n_groups, group_ptr[n_groups + 1], members[group_ptr[n_groups]]           the members of group g: members[group_ptr[g] .. group_ptr[g + 1])
+ *   *n_chunks, chunk_ptr[n_chunks + 1], chunk_group[n_chunks]                  chunk c: members[chunk_ptr[c] .. chunk_ptr[c + 1]) of chunk_group[c]
+ * Every output pointer may be NULL (call with the arrays NULL for the counts; N / 2 + 1, N, N + 1 and N entries always suffice).
+ * BA_ERR_ARG: N < 0, a NULL group_of with N > 0, chunk < 1. */
+int ba_intrinsics_group_plan(int N, const int *group_of, int chunk, int *n_groups, int *group_ptr, int *members, int *n_chunks, int *chunk_ptr,
+                             int *chunk_group);
+/* The cameras of a group solve for ONE f, k1, k2.  BA_ITERSCHUR, BA_F64 and BA_F32.  The unknowns keep their layout (D = 9 N): with P
+ * (9N x n_free) the matrix that copies a group's three intrinsics to rows 6..8 of each member, the step is dx_c = P y with
+ *   (P'SP) y = P' rhs,      S and rhs exactly what BA_ITERSCHUR solves without groups (lambda I inside S),
+ * computed as CG for Pi S on range(Pi), preconditioned by Pi M^-1, where Pi = P (P'P)^-1 P' replaces rows 6..8 of every member by the
+ * group's mean and M is the preconditioner in force (all three kinds of ba_solver_set_preconditioner are legal).  Nothing else changes:
+ * the linearisation, the point elimination, the back-substitution, the retraction and the LM control are the ungrouped solver's.
+ * Damping: lambda P'P, that is lambda n_g on the shared parameter of a group of n_g cameras -- Marquardt's damping of the stacked
+ * columns.  lambda0 = 1e-12 max diag J'J keeps its per-camera-column definition.
+ * What a caller sees: BA_GET_DX rows 6..8 are bit-equal inside a group, so f, k1, k2 of the members stay bit-equal through
+ * ba_solver_try_step, ba_solver_accept and ba_minimize; BA_GET_RHS returns Pi rhs; ba_solver_pcg_stats keeps its meaning with the
+ * residual |Pi (rhs - S dx_c)| / |Pi rhs|; BA_GET_GRAD, BA_GET_JC and the energy are per camera as before.  Priors, relative poses,
+ * losses, weights and masks are rows and columns of the same J: an intrinsics prior on one member acts on the shared parameter.
+ * group_of: N labels as for ba_intrinsics_group_plan (copied).  NULL, all negative, or no label used twice: no groups, and the solver
+ * enqueues the launches and returns the bits of one that never had any.  Takes effect at the next ba_solver_try_step / ba_minimize (the
+ * linearisation is untouched: no ba_solver_linearize needed); drops the captured trial graph like ba_solver_set_preconditioner.  A
+ * step that is pending is dropped, as ba_solver_set_state drops it: xTest belongs to the other group set, so ba_solver_accept returns
+ * BA_ERR_ARG until the next ba_solver_try_step.  BA_ERR_NOMEM: the host or device lists do not fit, the solver unchanged.  The
+ * chunk lists and partials are device buffers counted by ba_solver_device_bytes: 44 bytes per chunk slot (the chunks, plus at most 7
+ * empty slots in front of a group of 257 .. 2048 cameras), 4 per grouped camera, 4 per chunk of a group above 2048 cameras.
+ * BA_ERR_ARG, the solver unchanged: another kind; members of a group whose f, k1, k2 in the resident state (read back at the call, in
+ * the solver's scalar type) are not bit-equal -- equalise them with ba_solver_set_state first; members of a group that do not carry the
+ * same bits 6..8 of the ba_solver_set_constant mask in force.
+ * With groups in force, BA_ERR_ARG and nothing changed: ba_solver_set_state with unequal members; ba_solver_set_constant with intrinsics
+ * bits that differ inside a group; ba_solver_covariance_pcg (the covariance under groups is not built).
+ * Not built: a preconditioner that couples a group's pose blocks to its one intrinsics block (the arrowhead P'BP), the dense kinds,
+ * sharded solvers. */
+int ba_solver_set_shared_intrinsics(ba_solver *s, const int *group_of /* N, or NULL = none */);
+/* out4 = {groups, grouped cameras, cameras of the largest group, chunks}.  BA_ERR_ARG for another solver kind. */
+int ba_solver_shared_intrinsics_info(ba_solver *s, long long *out4);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);

@@ -140,7 +140,9 @@ __device__ __forceinline__ void ba_update_macro(int nrows, int ncols, int ld, in
                                                 const T *__restrict__ W1, const T *__restrict__ W2, T *__restrict__ As, T *__restrict__ Bs);
 
 // Panel step for block column p0: rows [p0, nrows), pivots [p0, min(p0 + 64, ncols)).
-//   S    : in place; on exit the block column holds L (strictly lower) and D (diagonal)
+//   S    : in place; on exit the rows below the diagonal block hold L.  The factored diagonal block itself (L strictly lower, D on the
+//          diagonal) is written back only when ONE workgroup runs the panel (the publish loop below); otherwise it stays in LDS --
+//          the sweep reads W, not L11 -- and S keeps what the trailing updates left there
 //   Wp   : ld x 64, column-major: Y = L D for the rows below the diagonal block (operand of the trailing update)
 //   Winv : 64 x 64 row-major: W = L11^-1 of this block (for the backward sweep)
 // Grid: one workgroup per 64 rows below the diagonal block (at least one).

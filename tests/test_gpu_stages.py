@@ -21,7 +21,8 @@ LDL^T and its back sweep only through the step (1e-6) or a normal-equations resi
                   GPU's dx and g
 
 Each value is printed as `STAGE <case> <metric> <value> <bound>`; the docstrings record the worst values measured on an MI355X.  The
-63 cases take 149 s on an MI355X box (most of it the quad assembly and residuals on the host).
+63 cases took 149 s on an MI355X box (most of it the quad assembly and residuals on the host); the 14 factor cases added since
+(N = 16 ... 71, 334: test_factor_and_sweep_backward_error) bring that test to 52 cases in 24 s.
 """
 import hashlib
 
@@ -172,10 +173,17 @@ FACTOR_CASES = [
     2, 3, 4, 5, 6, 7,
     # fused k_ldlt_step, the last block column 9 N mod 64 = 17, 35, 44, 53, 62, 7, 61, 15 wide (sub-panel counts 1 ... 4)
     9, 11, 12, 13, 14, 15, 21, 23,
+    # the sub-panel seams behind full block columns: N = 16, 32, 48 (D = 144, 288, 432) end in a block column 16, 32, 48 wide
+    16, 32, 48,
+    # N = 57 (D = 513): the last block column 1 wide beside the right-hand side row; N = 64 (D = 576 = 9 x 64): width 0, the right-hand
+    # side row alone in a tenth row block; N = 71 (D = 639): 63 wide
+    57, 64, 71,
     # N = 180: 26 block columns, k_ldlt_step with dyn_lds = 8192 throughout
     180,
-    # N = 240: 34 block columns (32 <= nblk < 48): the first four steps with dyn_lds = 0
+    # N = 240: 34 block columns (32 <= nblk < 48), more update jobs per launch than CUs (dyn_lds = 8192 in every step, like N = 180)
     240,
+    # N = 334: D = 3006, 47 block columns, the largest k_ldlt_step
+    334,
     # N = 340: 48 block columns, k_ldlt_step2 in single-panel mode from step 1 (p_single = 1)
     340,
     # N = 340 with BA_LDLT_PAIR_MIN=8: k_ldlt_step2's pair phase with 128 x 128 macro tiles up to step 41, then single-panel
@@ -192,7 +200,9 @@ def test_factor_and_sweep_backward_error(ba, O, gpu_ok, monkeypatch, case, scala
     and 10, on the branches of ba_ldlt_factor that run without a hand-off time-out (single block column, k_ldlt_step with and without
     dynamic LDS, k_ldlt_step2 single-panel and pair phase) behind the one-launch back sweep (k_ldlt_backflow); with it the point back-substitution, the retraction and the
     trial scalars of the same trials.  Measured worst eta, fp64 / fp32: one block column 5.6e-16 / 4.0e-6; k_ldlt_step (N = 9 ... 23,
-    180) 6.4e-16 / 5.2e-7; N = 240 1.8e-16 / 1.5e-8; N = 340 (single-panel and pair phase) 2.2e-16 / 1.5e-8; N = 600 1.4e-17 / 1.5e-8."""
+    180) 6.4e-16 / 5.2e-7; N = 240 1.8e-16 / 1.5e-8; N = 340 (single-panel and pair phase) 2.2e-16 / 1.5e-8; N = 600 1.4e-17 / 1.5e-8;
+    the seams N = 16, 32, 48, 57, 64, 71 6.5e-16 / 5.0e-7; N = 334 2.9e-16 / 1.5e-8.  The kernels alone, at every block shape and on
+    matrices that are no reduced camera matrix: test_gpu_ldlt_kernels.py."""
     if case == "340pair8":
         monkeypatch.setenv("BA_LDLT_PAIR_MIN", "8")
         ncams = 340

@@ -63,3 +63,12 @@ def test_relpose_harness_builds_with_the_library_flags(tmp_path):
     assert os.path.getsize(RH.build(tmp_path)) > 0
     ptr, inc = RH.csr(4, [(2, 0), (0, 1), (1, 2)])
     assert np.array_equal(ptr, [0, 2, 4, 6, 6]) and np.array_equal(inc, [1, 2, 3, 4, 0, 5])
+
+
+def test_ldlt_harness_builds_with_the_library_flags(tmp_path):
+    """tests/ldlt_harness.hip (test_gpu_ldlt_kernels.py's driver of the dense LDL^T of ba_dense.hip.h) compiles with csrc/Makefile's own
+    flags, and its driver sizes the buffers as ba_solver.hip does."""
+    import ldlt_harness as LH
+    assert os.path.getsize(LH.build(tmp_path)) > 0
+    assert LH.layout(9) == (64, 128, 128) and LH.layout(61) == (64, 128, 128) and LH.layout(62) == (128, 192, 192) and LH.layout(704) == (768, 832, 832)
+    assert LH.cov_layout(63) == (64, 127, 256, 128) and LH.cov_layout(130) == (192, 322, 448, 256)

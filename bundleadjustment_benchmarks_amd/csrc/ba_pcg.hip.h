@@ -31,6 +31,10 @@
 // members <- their mean) is launched on rhs in front of k_pcg_prec_inv and on z_0 behind it, on y = S p behind k_pcg_cam /
 // k_pcg_relpose, on z behind k_pcg_update (behind the forest's apply), and the partials of |rhs - y|^2 are formed again from the
 // projected y; the kernels of this file do not know about it.
+//
+// What ba_pcg_multi.hip.h (the nine-column PCG of ba_solver_covariance_pcg) computes alike it takes from here: ba_chol9 / ba_chol9_inverse
+// (a B_a's Cholesky and inverse), ba_pcg_dir (the direction formed on the fly), ba_dot9 (a block row by a 9-vector).  The chunk-order
+// sums are spelled out per kernel: their tails differ on purpose, and the order of a sum is behaviour here.
 #ifndef BA_PCG_HIP_H
 #define BA_PCG_HIP_H
 
@@ -58,6 +62,70 @@ __device__ __forceinline__ double ba_pcg_sum(const double *__restrict__ a, int n
     return block_reduce<double, false>(v, lds);
 }
 __device__ __forceinline__ int ba_pcg_slot(int k) { return k % 3; }
+// the search direction at o, formed on the fly: p_k = z_k + beta_k p_{k-1} (FINAL, the product S x: x)
+template <bool FINAL, typename T>
+__device__ __forceinline__ T ba_pcg_dir(const T *x, const T *z, const T *p, T beta, size_t o)
+{
+    return FINAL ? x[o] : z[o] + beta * p[o];
+}
+// one row of a 9 x 9 block by a 9-vector, summed from entry 0 up
+template <typename T> __device__ __forceinline__ T ba_dot9(const T *row, const T *v)
+{
+    T s = 0;
+#pragma unroll
+    for (int q = 0; q < 9; q++) s += row[q] * v[q];
+    return s;
+}
+// B = L L^T in place on the packed lower triangle, (i, j) at i (i + 1) / 2 + j.  False on a pivot <= 0 (FINITE: or not finite); a pivot
+// <= 0 is replaced by 1.
+template <bool FINITE> __device__ __forceinline__ bool ba_chol9(double (&L)[45])
+{
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        double d = L[j * (j + 1) / 2 + j];
+#pragma unroll
+        for (int k = 0; k < j; k++) d -= L[j * (j + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+        ok = ok && d > 0 && (!FINITE || d < INFINITY);
+        const double ljj = d > 0 ? sqrt(d) : 1.0;
+        L[j * (j + 1) / 2 + j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < 9; i++) {
+            double s = L[i * (i + 1) / 2 + j];
+#pragma unroll
+            for (int k = 0; k < j; k++) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+            L[i * (i + 1) / 2 + j] = s / ljj;
+        }
+    }
+    return ok;
+}
+// Mi = (L L^T)^-1 = W^T W, full 9 x 9, with W = L^-1 (packed lower)
+__device__ __forceinline__ void ba_chol9_inverse(const double (&L)[45], double (&Mi)[81])
+{
+    double W[45];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const double inv = 1.0 / L[i * (i + 1) / 2 + i];
+        W[i * (i + 1) / 2 + i] = inv;
+#pragma unroll
+        for (int j = 0; j < i; j++) {
+            double s = 0;
+#pragma unroll
+            for (int k = j; k < i; k++) s += L[i * (i + 1) / 2 + k] * W[k * (k + 1) / 2 + j];
+            W[i * (i + 1) / 2 + j] = -s * inv;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+            double s = 0;
+#pragma unroll
+            for (int k = i; k < 9; k++) s += W[k * (k + 1) / 2 + i] * W[k * (k + 1) / 2 + j];
+            Mi[9 * i + j] = s;
+            Mi[9 * j + i] = s;
+        }
+}
 
 // ---- once per trial: block-Jacobi preconditioner, reduced rhs, start of the recurrence --------------------------------------------------
 // Per camera chunk of <= 32 observations (one 32-lane group, lane = observation): the 45 lower-triangle entries of
@@ -170,49 +238,9 @@ __global__ __launch_bounds__(256) void k_pcg_prec_inv(int N, T *__restrict__ Bm,
         for (int i = 0; i < 9; i++)
 #pragma unroll
             for (int j = 0; j <= i; j++) L[i * (i + 1) / 2 + j] = (double)B[9 * i + j];
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < 9; j++) {
-            double d = L[j * (j + 1) / 2 + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) d -= L[j * (j + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
-            ok = ok && d > 0;
-            const double ljj = d > 0 ? sqrt(d) : 1.0;
-            L[j * (j + 1) / 2 + j] = ljj;
-#pragma unroll
-            for (int i = j + 1; i < 9; i++) {
-                double s = L[i * (i + 1) / 2 + j];
-#pragma unroll
-                for (int k = 0; k < j; k++) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
-                L[i * (i + 1) / 2 + j] = s / ljj;
-            }
-        }
         double Mi[81];
-        if (ok) {
-            double W[45]; // L^-1, packed lower
-#pragma unroll
-            for (int i = 0; i < 9; i++) {
-                const double inv = 1.0 / L[i * (i + 1) / 2 + i];
-                W[i * (i + 1) / 2 + i] = inv;
-#pragma unroll
-                for (int j = 0; j < i; j++) {
-                    double s = 0;
-#pragma unroll
-                    for (int k = j; k < i; k++) s += L[i * (i + 1) / 2 + k] * W[k * (k + 1) / 2 + j];
-                    W[i * (i + 1) / 2 + j] = -s * inv;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 9; i++)
-#pragma unroll
-                for (int j = 0; j <= i; j++) {
-                    double s = 0;
-#pragma unroll
-                    for (int k = i; k < 9; k++) s += W[k * (k + 1) / 2 + i] * W[k * (k + 1) / 2 + j];
-                    Mi[9 * i + j] = s;
-                    Mi[9 * j + i] = s;
-                }
-        } else {
+        if (ba_chol9<false>(L)) ba_chol9_inverse(L, Mi);
+        else {
 #pragma unroll
             for (int q = 0; q < 81; q++) Mi[q] = 0;
 #pragma unroll
@@ -229,7 +257,7 @@ __global__ __launch_bounds__(256) void k_pcg_prec_inv(int N, T *__restrict__ Bm,
         for (int i = 0; i < 9; i++) b[i] = rhs[9 * (size_t)a + i];
 #pragma unroll
         for (int i = 0; i < 9; i++) {
-            T zi = 0;
+            T zi = 0; // (not ba_dot9: in fp32 with FOREST the compiler then fuses products that it leaves unfused here)
 #pragma unroll
             for (int k = 0; k < 9; k++) zi += Mt[9 * i + k] * b[k];
             const size_t o = 9 * (size_t)a + i;
@@ -290,7 +318,7 @@ __global__ __launch_bounds__(256) void k_pcg_point(int k, int Ml, const int *__r
         const size_t c0 = 9 * (size_t)obs_cam[i];
 #pragma unroll
         for (int c = 0; c < 9; c++) {
-            const T v = FINAL ? x[c0 + c] : z[c0 + c] + beta * p[c0 + c];
+            const T v = ba_pcg_dir<FINAL>(x, z, p, beta, c0 + c);
             s0 += Z[3 * c] * v; s1 += Z[3 * c + 1] * v; s2 += Z[3 * c + 2] * v;
         }
     }
@@ -371,7 +399,7 @@ __global__ __launch_bounds__(256) void k_pcg_cam(int k, int N, const int *__rest
 #pragma unroll
         for (int q = 0; q < 9; q++) {
             const size_t o = 9 * a + q;
-            const T v = FINAL ? x[o] : z[o] + beta * p[o];
+            const T v = ba_pcg_dir<FINAL>(x, z, p, beta, o);
             t += Va[q] * v;
             if (q == r) vr = v;
         }
@@ -406,11 +434,11 @@ __global__ __launch_bounds__(256) void k_pcg_relpose(int k, int N, ba_relpose_cs
     const int r = (int)(idx - 9 * a);
     double acc = 0;
     if (a < (size_t)N) {
-        const T rp = ba_relpose_matvec_row<T>(cs, (int)a, r, [&](size_t o) { return FINAL ? x[o] : z[o] + beta * p[o]; });
+        const T rp = ba_relpose_matvec_row<T>(cs, (int)a, r, [&](size_t o) { return ba_pcg_dir<FINAL>(x, z, p, beta, o); });
         const T yr = y[9 * a + r] + rp;
         y[9 * a + r] = yr;
         if (FINAL) { const double d = (double)rhs[9 * a + r] - (double)yr; acc = d * d; }
-        else acc = (double)(z[9 * a + r] + beta * p[9 * a + r]) * (double)rp;
+        else acc = (double)ba_pcg_dir<false>(x, z, p, beta, 9 * a + r) * (double)rp;
     }
     acc = block_reduce<double, false>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = FINAL ? acc : part[blockIdx.x] + acc;
@@ -447,7 +475,7 @@ __global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__res
         const bool tree = FOREST && in_tree[a]; // (z and r'z of this camera: k_pcg_forest_apply, directly behind)
 #pragma unroll
         for (int i = 0; i < 9; i++) {
-            T zi = 0;
+            T zi = 0; // (not ba_dot9: the fp32 FOREST instantiation then needs 82 registers instead of 80, one wave less per SIMD)
 #pragma unroll
             for (int q = 0; q < 9; q++) zi += Mi[9 * i + q] * rv[q];
             if (!tree) {

@@ -24,11 +24,13 @@
 // column's bits do not depend on what shares its batch.  A column that is done (converged, or a zero right-hand side) is frozen:
 // k_mc_update leaves its x, r, z, p alone.  No workgroup waits for another.  Every launch returns at once when all columns are done
 // or a singular flag is up; the host enqueues rounds of iterations and reads the state word back between them.
+//
+// The arithmetic is the trial's (ba_pcg.hip.h: ba_chol9, ba_chol9_inverse, ba_pcg_dir, ba_dot9); the kernels stay apart from their
+// k_pcg_* counterparts because their loop control differs.
 #ifndef BA_PCG_MULTI_HIP_H
 #define BA_PCG_MULTI_HIP_H
 
-#include "ba_kernels.hip.h"
-#include "ba_relpose.hip.h"
+#include "ba_pcg.hip.h" /* ba_chol9, ba_chol9_inverse, ba_pcg_dir, ba_dot9 */
 
 #define BA_MC_NR 9   /* columns of a batch */
 #define BA_MC_CPB 28 /* cameras per workgroup of the camera kernels (28 x 9 = 252 threads of 256) */
@@ -83,47 +85,11 @@ __global__ __launch_bounds__(256) void k_mc_prec_inv(int N, double *__restrict__
             const bool fx = ((cm >> i) | (cm >> j)) & 1u;
             L[i * (i + 1) / 2 + j] = fx ? (i == j ? 1.0 : 0.0) : B[9 * i + j];
         }
-    bool ok = true;
+    if (!ba_chol9<true>(L)) *flag = 1; // (every writer stores the same value)
+    double Mi[81];
+    ba_chol9_inverse(L, Mi);
 #pragma unroll
-    for (int j = 0; j < 9; j++) {
-        double d = L[j * (j + 1) / 2 + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= L[j * (j + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
-        ok = ok && d > 0 && d < INFINITY;
-        const double ljj = d > 0 ? sqrt(d) : 1.0;
-        L[j * (j + 1) / 2 + j] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < 9; i++) {
-            double s = L[i * (i + 1) / 2 + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
-            L[i * (i + 1) / 2 + j] = s / ljj;
-        }
-    }
-    if (!ok) *flag = 1; // (every writer stores the same value)
-    double W[45];       // L^-1, packed lower
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        const double inv = 1.0 / L[i * (i + 1) / 2 + i];
-        W[i * (i + 1) / 2 + i] = inv;
-#pragma unroll
-        for (int j = 0; j < i; j++) {
-            double s = 0;
-#pragma unroll
-            for (int k = j; k < i; k++) s += L[i * (i + 1) / 2 + k] * W[k * (k + 1) / 2 + j];
-            W[i * (i + 1) / 2 + j] = -s * inv;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 9; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-            double s = 0;
-#pragma unroll
-            for (int k = i; k < 9; k++) s += W[k * (k + 1) / 2 + i] * W[k * (k + 1) / 2 + j];
-            B[9 * i + j] = s;
-            B[9 * j + i] = s;
-        }
+    for (int q = 0; q < 81; q++) B[q] = Mi[q];
 }
 
 // ---- right-hand sides (the vector is zeroed in front) ------------------------------------------------------------------------------------
@@ -198,9 +164,7 @@ __global__ __launch_bounds__(256) void k_mc_init(int N, const double *__restrict
         for (int q = 0; q < 9; q++) b[q] = rhs[o + BA_MC_NR * q];
 #pragma unroll
         for (int i = 0; i < 9; i++) {
-            double zi = 0;
-#pragma unroll
-            for (int q = 0; q < 9; q++) zi += Mi[9 * i + q] * b[q];
+            const double zi = ba_dot9(Mi + 9 * i, b);
             x[o + BA_MC_NR * i] = 0; r[o + BA_MC_NR * i] = b[i]; z[o + BA_MC_NR * i] = zi; p[o + BA_MC_NR * i] = 0;
             rz += b[i] * zi;
             rr += b[i] * b[i];
@@ -278,7 +242,7 @@ __global__ __launch_bounds__(256) void k_mc_point(int Ml, const int *__restrict_
 #pragma unroll
             for (int c = 0; c < BA_MC_NR; c++) {
                 const size_t o = c0 + BA_MC_NR * q + c;
-                const double v = FINAL ? x[o] : z[o] + beta[c] * p[o];
+                const double v = ba_pcg_dir<FINAL>(x, z, p, beta[c], o);
                 s[0][c] += z0 * v; s[1][c] += z1 * v; s[2][c] += z2 * v;
             }
         }
@@ -359,7 +323,7 @@ __global__ __launch_bounds__(256) void k_mc_cam(int N, const int *__restrict__ c
         double v[9], s[9];
 #pragma unroll
         for (int q = 0; q < 9; q++) {
-            v[q] = FINAL ? x[o + BA_MC_NR * q] : z[o + BA_MC_NR * q] + beta * p[o + BA_MC_NR * q];
+            v[q] = ba_pcg_dir<FINAL>(x, z, p, beta, o + BA_MC_NR * q);
             s[q] = 0;
         }
         for (int g = cam_dchunk_ptr[a], g1 = cam_dchunk_ptr[a + 1]; g < g1; g++) {
@@ -371,14 +335,11 @@ __global__ __launch_bounds__(256) void k_mc_cam(int N, const int *__restrict__ c
         const unsigned cm = cmask ? (unsigned)cmask[a] : 0u;
 #pragma unroll
         for (int i = 0; i < 9; i++) {
-            double t = 0;
-#pragma unroll
-            for (int q = 0; q < 9; q++) t += Va[9 * i + q] * v[q];
+            const double t = ba_dot9(Va + 9 * i, v);
             double yi = (t + lambda * v[i]) - s[i];
             if (RP)
                 yi += ba_relpose_matvec_row<double>(cs, a, i, [&](size_t u) {
-                    const size_t ou = u * BA_MC_NR + c;
-                    return FINAL ? x[ou] : z[ou] + beta * p[ou];
+                    return ba_pcg_dir<FINAL>(x, z, p, beta, u * BA_MC_NR + c);
                 });
             if ((cm >> i) & 1u) yi = v[i]; // a fixed parameter's row of the operator is the identity (v is 0 there throughout)
             y[o + BA_MC_NR * i] = yi;
@@ -433,9 +394,7 @@ __global__ __launch_bounds__(256) void k_mc_update(int N, const double *__restri
         }
 #pragma unroll
         for (int i = 0; i < 9; i++) {
-            double zi = 0;
-#pragma unroll
-            for (int q = 0; q < 9; q++) zi += Mi[9 * i + q] * rv[q];
+            const double zi = ba_dot9(Mi + 9 * i, rv);
             z[o + BA_MC_NR * i] = zi;
             rz += rv[i] * zi;
             rr += rv[i] * rv[i];

@@ -57,6 +57,13 @@ enum { EV_T0 = 0, EV_T1, EV_T2, EV_T3, EV_T4, EV_T5, EV_T6, EV_L0, EV_L1, EV_N }
 constexpr int RING_EV = 8; // event slots of the trials in flight under ba_minimize (LM_DEPTH + the ones not yet harvested)
 constexpr int RING_NE = 6; // per slot: trial start | before / after the matrix all-reduce | before / after the scalar all-reduce | after control + linearisation
 
+// a run-time flag as a template argument: with_flag(b, [&](auto B) { launch k<..., B()> with one argument list })
+template <typename F> void with_flag(bool b, F &&f)
+{
+    if (b) f(std::bool_constant<true>{});
+    else f(std::bool_constant<false>{});
+}
+
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
@@ -986,10 +993,9 @@ template <typename T> struct Solver final : SolverBase {
     }
     void launch_forest_factor()
     {
-        if (fo.width == 9)
-            hipLaunchKernelGGL((k_pcg_forest_factor<T, 9>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
-        else
-            hipLaunchKernelGGL((k_pcg_forest_factor<T>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+        with_flag(fo.width == 9, [&](auto W9) {
+            hipLaunchKernelGGL((k_pcg_forest_factor<T, W9() ? 9 : 6>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+        });
     }
     template <bool START> void launch_forest_apply(double *part)
     {
@@ -1250,15 +1256,16 @@ template <typename T> struct Solver final : SolverBase {
     {
         launch_pcg_blocks();
         if (share_on()) launch_share<false>(d_pcg_b.p); // rhs <- Pi rhs: r_0, |rhs|^2 and z_0 see it (BA_GET_RHS returns it)
-        if (forest_on()) { // the factor reads B_a in front of its inversion in place; z_0 and r_0'z_0 of the trees behind it
+        const bool forest = forest_on(); // the factor reads B_a in front of its inversion in place; z_0 and r_0'z_0 of the trees behind it
+        if (forest) {
             if (fo.width == 9) launch_forest_edges(); // (behind the elimination's and the constraints' records)
             launch_forest_factor();
-            hipLaunchKernelGGL((k_pcg_prec_inv<T, true>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
-                               pcg_part_rz(), pcg_part_rr(), (const unsigned char *)fo.in_tree.p);
-            launch_forest_apply<true>(pcg_part_rz() + pcg_gc);
-        } else
-            hipLaunchKernelGGL((k_pcg_prec_inv<T>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
-                               pcg_part_rz(), pcg_part_rr(), (const unsigned char *)nullptr);
+        }
+        with_flag(forest, [&](auto FOREST) {
+            hipLaunchKernelGGL((k_pcg_prec_inv<T, FOREST()>), dim3(pcg_gc), dim3(256), 0, st, N, d_pcg_M.p, d_pcg_b.p, d_dxc.p, d_pcg_r.p, d_pcg_z.p, d_pcg_p.p,
+                               pcg_part_rz(), pcg_part_rr(), FOREST() ? (const unsigned char *)fo.in_tree.p : nullptr);
+        });
+        if (forest) launch_forest_apply<true>(pcg_part_rz() + pcg_gc);
         if (share_on()) launch_share<false>(d_pcg_z.p); // z_0 <- Pi z_0 (r_0'z_0 of the unprojected z_0 is r_0'(Pi z_0): r_0 is in range(Pi))
         hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(256), 0, st, pcg_part_rr(), pcg_gc, d_pcg.p);
     }
@@ -1291,14 +1298,12 @@ template <typename T> struct Solver final : SolverBase {
         const double tol2 = pcg_rel_tol * pcg_rel_tol;
         for (int k = 0; k < pcg_max_iter; k++) {
             launch_pcg_matvec<false>(k, tol2);
-            if (forest_on()) {
-                hipLaunchKernelGGL((k_pcg_update<T, true>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p,
+            with_flag(forest_on(), [&](auto FOREST) {
+                hipLaunchKernelGGL((k_pcg_update<T, FOREST()>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p,
                                    d_pcg_r.p, pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p,
-                                   (const unsigned char *)fo.in_tree.p);
-                launch_forest_apply<false>(pcg_part_rz() + (size_t)((k + 1) % 3) * pcg_gz() + pcg_gc);
-            } else
-                hipLaunchKernelGGL((k_pcg_update<T>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, d_pcg_r.p,
-                                   pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p, (const unsigned char *)nullptr);
+                                   FOREST() ? (const unsigned char *)fo.in_tree.p : nullptr);
+            });
+            if (forest_on()) launch_forest_apply<false>(pcg_part_rz() + (size_t)((k + 1) % 3) * pcg_gz() + pcg_gc);
             if (share_on()) launch_share<true>(d_pcg_z.p); // z_{k+1} <- Pi z_{k+1}, behind whatever produced it
         }
         launch_pcg_matvec<true>(pcg_max_iter, tol2);
@@ -1364,6 +1369,33 @@ template <typename T> struct Solver final : SolverBase {
     T *cov_dxsave() const { return cov_sc() + Dp; }
     size_t cov_count() const { return cov_nmat() + (size_t)cov_ld() * NB + (size_t)((D + NB - 1) / NB) * NB * NB + 2 * (size_t)Dp + d_dxc.n; }
 
+    // What both covariance routes start from, at the lambda in SC_LAMBDA: the elimination, a fixed point's records cleared (its
+    // U_p = lambda I is never inverted: its records are the zeros they stand for), every free point's block checked into *flag
+    void launch_cov_eliminate(int *flag)
+    {
+        launch_eliminate();
+        if (masked && d_pfix.p)
+            hipLaunchKernelGGL((k_cov_fixed_records<T>), dim3((std::max(Kl, Ml) + 255) / 256), dim3(256), 0, st, Kl, Ml, (int)BA_REC, (const int *)d_obs_pt.p,
+                               (const unsigned char *)d_pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
+        if (Ml <= 0) return;
+        if (priors()) // (a point prior is in U0 and in no observation's Jp)
+            hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)d_pfix.p,
+                               (const T *)(d_scal.p + SC_LAMBDA), flag);
+        else
+            hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
+                               (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), flag);
+    }
+    // a request for blocks: counts, null pointers, index ranges (single shard: the shard's points are the problem's)
+    bool cov_request_ok(int n_pairs, const int *cam_pairs, const double *cam_cov, int n_pts, const int *pt_ids, const double *pt_cov) const
+    {
+        if (n_pairs < 0 || n_pts < 0 || (n_pairs > 0 && (!cam_pairs || !cam_cov)) || (n_pts > 0 && (!pt_ids || !pt_cov))) return false;
+        for (int q = 0; q < 2 * n_pairs; q++)
+            if (cam_pairs[q] < 0 || cam_pairs[q] >= N) return false;
+        for (int q = 0; q < n_pts; q++)
+            if (pt_ids[q] < 0 || pt_ids[q] >= Ml) return false;
+        return true;
+    }
+
     int cov_compute(double lambda) override
     {
         if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG; // (a single-precision inverse at these condition numbers is noise)
@@ -1388,22 +1420,13 @@ template <typename T> struct Solver final : SolverBase {
             // S(lambda) as a trial assembles it (segment A + the diagonal's lambda), left unfactored in d_S.  The assembly arms the back
             // sweep's hand-over vector, which is where the last trial's dx_c lives (BA_GET_DX): kept aside and put back.
             HIPCHK(hipMemcpyAsync(cov_dxsave(), d_dxc.p, sizeof(T) * d_dxc.n, hipMemcpyDeviceToDevice, st));
-            launch_eliminate();
-            if (masked && d_pfix.p) // (a fixed point's U_p = lambda I is never inverted: its records are the zeros they stand for)
-                hipLaunchKernelGGL((k_cov_fixed_records<T>), dim3((std::max(Kl, Ml) + 255) / 256), dim3(256), 0, st, Kl, Ml, (int)BA_REC, (const int *)d_obs_pt.p,
-                                   (const unsigned char *)d_pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
+            launch_cov_eliminate(d_cov_flag.p);
             launch_schur();
             launch_post_reduce();
             HIPCHK(hipMemcpyAsync(d_dxc.p, cov_dxsave(), sizeof(T) * d_dxc.n, hipMemcpyDeviceToDevice, st));
             HIPCHK(hipMemsetAsync(d_cov.p, 0, sizeof(T) * cov_nmat(), st));
             hipLaunchKernelGGL((k_cov_scale<T>), dim3((D + 255) / 256), dim3(256), 0, st, D, ld, (const T *)d_S.p, (const unsigned short *)d_cmask.p,
                                cov_sc(), d_cov_flag.p);
-            if (priors()) // (a point prior is in U0 and in no observation's Jp)
-                hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)d_pfix.p,
-                                   (const T *)(d_scal.p + SC_LAMBDA), d_cov_flag.p);
-            else
-            hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
-                               (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), d_cov_flag.p);
             hipLaunchKernelGGL((k_cov_stage<T>), dim3(((D + NB - 1) / NB) * NB), dim3(256), 0, st, D, Dp, ld, (const T *)d_S.p, (const T *)cov_sc(), ldc, d_cov.p);
             HIPCHK(hipEventRecord(ev[EV_T1], st));
             HIPCHK(hipMemcpyAsync(&flag, d_cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1431,11 +1454,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG;
         else {
-            if (!cov_valid || n_pairs < 0 || n_pts < 0 || (n_pairs > 0 && (!cam_pairs || !cam_cov)) || (n_pts > 0 && (!pt_ids || !pt_cov))) return BA_ERR_ARG;
-            for (int q = 0; q < 2 * n_pairs; q++)
-                if (cam_pairs[q] < 0 || cam_pairs[q] >= N) return BA_ERR_ARG;
-            for (int q = 0; q < n_pts; q++)
-                if (pt_ids[q] < 0 || pt_ids[q] >= Ml) return BA_ERR_ARG; // (single shard: the shard's points are the problem's)
+            if (!cov_valid || !cov_request_ok(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov)) return BA_ERR_ARG;
             const int ldc = cov_ld();
             int rc;
             HIPCHK(hipStreamSynchronize(st));
@@ -1533,16 +1552,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipMemsetAsync(&ms->flag, 0, sizeof(int), st));
         if ((rc = set_lambda((T)lambda))) return rc;
         HIPCHK(hipEventRecord(ev[EV_T0], st));
-        launch_eliminate();
-        if (masked && d_pfix.p)
-            hipLaunchKernelGGL((k_cov_fixed_records<T>), dim3((std::max(Kl, Ml) + 255) / 256), dim3(256), 0, st, Kl, Ml, (int)BA_REC, (const int *)d_obs_pt.p,
-                               (const unsigned char *)d_pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
-        if (priors() && Ml > 0)
-            hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)d_pfix.p,
-                               (const T *)(d_scal.p + SC_LAMBDA), &ms->flag);
-        else if (Ml > 0)
-            hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
-                               (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), &ms->flag);
+        launch_cov_eliminate(&ms->flag);
         launch_pcg_blocks((T *)d_mc_M.p, (T *)c.y, (T *)c.z);
         hipLaunchKernelGGL(k_mc_prec_inv, dim3((N + 255) / 256), dim3(256), 0, st, N, d_mc_M.p, c.cmask, &ms->flag);
         ba_mc_dev h{};
@@ -1563,14 +1573,11 @@ template <typename T> struct Solver final : SolverBase {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_mc_cam_chunks<FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, (const int *)d_dchunk_ptr.p,
                                (const int *)d_cam_obs.p, (const int *)d_obs_pt.p, (const double *)d_rec.p, (const double *)d_mc_w.p, d_mc_slab.p, ms);
-        if (relposes())
-            hipLaunchKernelGGL((k_mc_cam<FINAL, true>), dim3(c.gm), dim3(256), 0, st, N, (const int *)d_cam_dchunk_ptr.p, (const double *)d_mc_slab.p,
+        with_flag(relposes(), [&](auto RP) {
+            hipLaunchKernelGGL((k_mc_cam<FINAL, RP()>), dim3(c.gm), dim3(256), 0, st, N, (const int *)d_cam_dchunk_ptr.p, (const double *)d_mc_slab.p,
                                (const double *)d_V.p, lam, (const double *)c.z, (const double *)c.p, (const double *)c.x, (const double *)c.b,
-                               relpose_csr(), c.cmask, c.y, c.part_py, ms);
-        else
-            hipLaunchKernelGGL((k_mc_cam<FINAL, false>), dim3(c.gm), dim3(256), 0, st, N, (const int *)d_cam_dchunk_ptr.p, (const double *)d_mc_slab.p,
-                               (const double *)d_V.p, lam, (const double *)c.z, (const double *)c.p, (const double *)c.x, (const double *)c.b,
-                               ba_relpose_csr<double>{nullptr, nullptr, nullptr, nullptr}, c.cmask, c.y, c.part_py, ms);
+                               RP() ? relpose_csr() : ba_relpose_csr<double>{nullptr, nullptr, nullptr, nullptr}, c.cmask, c.y, c.part_py, ms);
+        });
         hipLaunchKernelGGL((k_mc_alpha<FINAL>), dim3(1), dim3(256), 0, st, c.gm, (const double *)c.part_py, d_mc.p);
     }
     // One batch, its right-hand sides in c.b (`live` of them not zero): rounds of iterations with the state read back between them,
@@ -1638,13 +1645,8 @@ template <typename T> struct Solver final : SolverBase {
         else {
             // refusals: host side, before any launch
             if (!iterative() || sharded() || share_on() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
-                !(rel_tol >= 0 && rel_tol < 1) || n_pairs < 0 || n_pts < 0 || (n_pairs > 0 && (!cam_pairs || !cam_cov)) ||
-                (n_pts > 0 && (!pt_ids || !pt_cov)))
+                !(rel_tol >= 0 && rel_tol < 1) || !cov_request_ok(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov))
                 return BA_ERR_ARG;
-            for (int q = 0; q < 2 * n_pairs; q++)
-                if (cam_pairs[q] < 0 || cam_pairs[q] >= N) return BA_ERR_ARG;
-            for (int q = 0; q < n_pts; q++)
-                if (pt_ids[q] < 0 || pt_ids[q] >= Ml) return BA_ERR_ARG;
             int rc;
             McRun c;
             if ((rc = mc_begin(max_iter ? max_iter : pcg_max_iter, rel_tol != 0 ? rel_tol : pcg_rel_tol, c))) return rc;
@@ -2077,8 +2079,9 @@ template <typename T> struct Solver final : SolverBase {
         int rc;
         if (!d_pack.p && (rc = d_pack.alloc(npk + 1))) return rc;
         const dim3 gpk((Dp + 255) / 256 > 8 ? 8 : (Dp + 255) / 256, Dp);
-        if (unpack) hipLaunchKernelGGL((k_pack_lower<T, true>), gpk, dim3(256), 0, st, Dp, ld, d_S.p, d_pack.p, npk, d_scal.p, (int)SC_ELOC, (int)SC_ENERGY);
-        else hipLaunchKernelGGL((k_pack_lower<T, false>), gpk, dim3(256), 0, st, Dp, ld, d_S.p, d_pack.p, npk, d_scal.p, (int)SC_ELOC, (int)SC_ENERGY);
+        with_flag(unpack, [&](auto UNPACK) {
+            hipLaunchKernelGGL((k_pack_lower<T, UNPACK()>), gpk, dim3(256), 0, st, Dp, ld, d_S.p, d_pack.p, npk, d_scal.p, (int)SC_ELOC, (int)SC_ENERGY);
+        });
         return BA_OK;
     }
 
@@ -2120,14 +2123,11 @@ template <typename T> struct Solver final : SolverBase {
         if ((rc = mark(EV_T4))) return rc;
         launch_backsub_retract();
         if (d_pr_lonely.n > 0) { // (points with a prior and no observation: none on a usual problem, no launch then)
-            if (masked)
-                hipLaunchKernelGGL((k_prior_lonely<T, true>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
+            with_flag(masked, [&](auto MASKED) {
+                hipLaunchKernelGGL((k_prior_lonely<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
                                    (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p, d_part_bs.p, gB,
-                                   (const unsigned char *)d_pfix.p);
-            else
-                hipLaunchKernelGGL((k_prior_lonely<T, false>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
-                                   (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p, d_part_bs.p, gB,
-                                   (const unsigned char *)nullptr);
+                                   MASKED() ? (const unsigned char *)d_pfix.p : nullptr);
+            });
         }
         if ((rc = mark(EV_T5))) return rc;
         launch_test_energy(step_level || !ctl_reduces()); // (single shard: k_lm_control sums the three partial arrays at its head)

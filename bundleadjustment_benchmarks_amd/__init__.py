@@ -29,6 +29,9 @@ LOSS_REFERENCE, LOSS_TRIVIAL, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2, 3
 # or + the blocks S_ab of a maximum-weight spanning forest of the co-visibility graph (Problem.covisibility)
 PRECOND_BLOCK_JACOBI, PRECOND_CONSTRAINT_FOREST, PRECOND_VISIBILITY_FOREST = 0, 1, 3  # (2 is no kind: refused as before)
 
+# ba_solver_set_damping: lambda I (the reference's, a new solver's) or Marquardt's lambda diag(J'J), clamped (CHOLESKY, ITERSCHUR)
+DAMP_IDENTITY, DAMP_MARQUARDT = 0, 1
+
 (GET_RESIDUALS, GET_JC, GET_JP, GET_GRAD, GET_S, GET_RHS, GET_DX, GET_CAMS, GET_POINTS, GET_CAMS_TEST,
  GET_POINTS_TEST) = range(11)
 
@@ -47,6 +50,7 @@ EXPORTS = [
     "ba_solver_set_relative_poses", "ba_solver_relative_pose_energy",
     "ba_solver_set_preconditioner", "ba_solver_preconditioner_info", "ba_relpose_forest_plan", "ba_problem_covisibility",
     "ba_intrinsics_group_plan", "ba_solver_set_shared_intrinsics", "ba_solver_shared_intrinsics_info",
+    "ba_solver_set_damping", "ba_solver_get_damping",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -140,6 +144,8 @@ def lib():
         L.ba_solver_recoveries.argtypes = [C.c_void_p]
         L.ba_solver_set_pcg.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.ba_solver_pcg_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ba_solver_set_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        L.ba_solver_get_damping.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_constant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_problem_gauge_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -369,6 +375,18 @@ class Solver:
     def set_pcg(self, max_iter, rel_tol):
         """ITERSCHUR: at most max_iter PCG iterations per trial, stop at |r| <= rel_tol |rhs|."""
         _chk(lib().ba_solver_set_pcg(self._h, int(max_iter), float(rel_tol)), "ba_solver_set_pcg")
+
+    def set_damping(self, kind, diag_min=0.0, diag_max=0.0):
+        """DAMP_IDENTITY (a new solver's: lambda I) or DAMP_MARQUARDT: a trial solves (J'J + lambda D) dx = -J'e with
+        D_ii = min(max((J'J)_ii, diag_min), diag_max); 0 = the library's defaults (1e-6, 1e32).  lambda is then dimensionless and
+        minimize() starts from LMParams.lambda_init.  CHOLESKY and ITERSCHUR, one shard; takes effect at the next try_step() / minimize()."""
+        _chk(lib().ba_solver_set_damping(self._h, int(kind), float(diag_min), float(diag_max)), "ba_solver_set_damping")
+
+    def damping(self):
+        """(kind, diag_min, diag_max) in force."""
+        k, lo, hi = C.c_int(), C.c_double(), C.c_double()
+        _chk(lib().ba_solver_get_damping(self._h, C.byref(k), C.byref(lo), C.byref(hi)), "ba_solver_get_damping")
+        return int(k.value), float(lo.value), float(hi.value)
 
     def set_preconditioner(self, kind, max_tree=0):
         """ITERSCHUR: PRECOND_BLOCK_JACOBI (a new solver's), PRECOND_CONSTRAINT_FOREST or PRECOND_VISIBILITY_FOREST with at most max_tree

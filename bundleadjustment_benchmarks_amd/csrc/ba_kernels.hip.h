@@ -84,18 +84,37 @@ template <typename T> __device__ __forceinline__ void ba_pt_terms(const T (&B)[6
 }
 // U + lambda I = L D L^T (3 x 3, no pivoting), t = L^-1 g  (BacktrackLevMarqCholesky.h:274-282, point columns first)
 template <typename T> struct ba_chol3_t { T l10, l20, l21, i0, i1, i2, t0, t1, t2; };
-template <typename T> __device__ __forceinline__ ba_chol3_t<T> ba_chol3(T u0, T u1, T u2, T u3, T u4, T u5, T g0, T g1, T g2, T lambda)
+// The three pivots take their own dampings l0, l1, l2, added in the order below: lambda three times for lambda I, or, under Marquardt's
+// damping (ba_solver_set_damping), d_q = fl(lambda clamp(u_qq)).
+template <typename T> __device__ __forceinline__ ba_chol3_t<T> ba_chol3(T u0, T u1, T u2, T u3, T u4, T u5, T g0, T g1, T g2, T l0, T l1, T l2)
 {
 #pragma clang fp contract(off)
     ba_chol3_t<T> c;
-    const T d0 = u0 + lambda;
+    const T d0 = u0 + l0;
     c.l10 = u1 / d0; c.l20 = u2 / d0;
-    const T d1 = ba_fma(-(c.l10 * c.l10), d0, u3 + lambda);
+    const T d1 = ba_fma(-(c.l10 * c.l10), d0, u3 + l1);
     c.l21 = ba_fma(-(c.l20 * c.l10), d0, u4) / d1;
-    const T d2 = ba_fma(-(c.l21 * c.l21), d1, ba_fma(-(c.l20 * c.l20), d0, u5 + lambda));
+    const T d2 = ba_fma(-(c.l21 * c.l21), d1, ba_fma(-(c.l20 * c.l20), d0, u5 + l2));
     c.i0 = (T)1.0 / d0; c.i1 = (T)1.0 / d1; c.i2 = (T)1.0 / d2;
     c.t0 = g0; c.t1 = ba_fma(-c.l10, c.t0, g1); c.t2 = ba_fma(-c.l21, c.t1, ba_fma(-c.l20, c.t0, g2));
     return c;
+}
+template <typename T> __device__ __forceinline__ ba_chol3_t<T> ba_chol3(T u0, T u1, T u2, T u3, T u4, T u5, T g0, T g1, T g2, T lambda)
+{
+    return ba_chol3<T>(u0, u1, u2, u3, u4, u5, g0, g1, g2, lambda, lambda, lambda);
+}
+// The damping of one parameter: lambda itself (MARQ = false: the argument comes back, nothing is computed), or
+// fl(lambda min(max(diag, dmin), dmax)) -- one rounding of its own, whatever sum it joins (contraction is off here).
+// The bounds travel as kernel arguments behind the ones the identity instantiations always had.
+template <typename T> struct ba_damp_args { T dmin, dmax; };
+template <bool MARQ, typename T> __device__ __forceinline__ T ba_damp(T lambda, T diag, ba_damp_args<T> da)
+{
+#pragma clang fp contract(off)
+    if constexpr (!MARQ) return lambda;
+    else {
+        const T c = diag < da.dmin ? da.dmin : diag;
+        return lambda * (c > da.dmax ? da.dmax : c);
+    }
 }
 // The observation's record: Z = A^T (B L^-T) (9 x 3 row-major), the point's 1 / D, pad -- one burst of 16-byte stores.
 // The record (30 of its 32 scalars) leaves in one burst at the end: a record is two cache lines that only this thread writes, and
@@ -631,12 +650,14 @@ template <typename T> __global__ __launch_bounds__(256) void k_vdiag(int N, cons
 // U_j + lambda I = L D L^T;  Z_i = A_i^T (B_i L^-T) = W_i L^-T;  t = L^-1 g_p.  One thread per observation (each
 // recomputes its point's 3x3 LDL^T: 20 flops, cheaper than a second launch); the first observation of a point also
 // writes the per-point factors.
-template <typename T>
+// MARQ (ba_solver_set_damping): the pivots are damped by fl(lambda clamp(U0[0, 3, 5])) of the point instead of lambda.
+template <typename T, bool MARQ = false>
 __global__ __launch_bounds__(256) void k_elim_chol(int K, int Ml, const int *__restrict__ obs_pt, const int *__restrict__ pt_ptr,
                                                    const T *__restrict__ JcA /* [K][20] */, const T *__restrict__ Jp, const T *__restrict__ U0,
                                                    const T *__restrict__ gp, const T *__restrict__ lam, T *__restrict__ rec,
                                                    T *__restrict__ dinv, T *__restrict__ tvec, T *__restrict__ tri,
-                                                   const int *__restrict__ fresh = nullptr /* != 0: the fused linearisation has left this trial's records */)
+                                                   const int *__restrict__ fresh = nullptr /* != 0: the fused linearisation has left this trial's records */,
+                                                   ba_damp_args<T> da = ba_damp_args<T>{})
 {
     if (fresh && *fresh != 0) return; // (uniform)
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -644,8 +665,14 @@ __global__ __launch_bounds__(256) void k_elim_chol(int K, int Ml, const int *__r
     const T lambda = *lam;
     const int j = obs_pt[i];
     const size_t M = (size_t)Ml;
-    const ba_chol3_t<T> c3 = ba_chol3<T>(U0[j], U0[M + j], U0[2 * M + j], U0[3 * M + j], U0[4 * M + j], U0[5 * M + j],
-                                         gp[j], gp[M + j], gp[2 * M + j], lambda);
+    ba_chol3_t<T> c3;
+    if constexpr (MARQ) {
+        const T u0 = U0[j], u3 = U0[3 * M + j], u5 = U0[5 * M + j];
+        c3 = ba_chol3<T>(u0, U0[M + j], U0[2 * M + j], u3, U0[4 * M + j], u5, gp[j], gp[M + j], gp[2 * M + j],
+                         ba_damp<true, T>(lambda, u0, da), ba_damp<true, T>(lambda, u3, da), ba_damp<true, T>(lambda, u5, da));
+    } else
+        c3 = ba_chol3<T>(U0[j], U0[M + j], U0[2 * M + j], U0[3 * M + j], U0[4 * M + j], U0[5 * M + j],
+                         gp[j], gp[M + j], gp[2 * M + j], lambda);
     if (i == pt_ptr[j]) {
         dinv[j] = c3.i0; dinv[M + j] = c3.i1; dinv[2 * M + j] = c3.i2;
         tvec[j] = c3.t0; tvec[M + j] = c3.t1; tvec[2 * M + j] = c3.t2;
@@ -1197,12 +1224,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 // (Eight lanes per output, their partial sums meeting in a butterfly, were measured here and in k_cam_gram_reduce: config 2 7250 ->
 // 7740 LM it/s -- but another order of additions, and at lambda <= 1e-9 (cond 1e19 and worse) that is enough to move single trials
 // of the referee tests across their bounds.  The order of the additions stays; only more of their loads are in flight.)
-template <typename T>
+// MARQ (ba_solver_set_damping, single shard only): the diagonal gets fl(lambda clamp(V_qq)) instead of lambda, (V - s) + d as before.
+template <typename T, bool MARQ = false>
 __global__ __launch_bounds__(192) void k_schur_reduce(int nred, const int *__restrict__ red_pairs, int D, int ld, const int *__restrict__ pair_hi,
                                                       const int *__restrict__ pair_lo, const int *__restrict__ pair_chunk_ptr,
                                                       const T *__restrict__ slab, const T *__restrict__ V,
                                                       const T *__restrict__ gc, T *__restrict__ S, const T *__restrict__ lam = nullptr,
-                                                      int post_blocks = 0, int Dp = 0, T *__restrict__ gc_out = nullptr, T *__restrict__ xarm = nullptr)
+                                                      int post_blocks = 0, int Dp = 0, T *__restrict__ gc_out = nullptr, T *__restrict__ xarm = nullptr,
+                                                      ba_damp_args<T> da = ba_damp_args<T>{})
 {
     if (post_blocks && blockIdx.x >= gridDim.x - post_blocks) { // one wave per column (k_post_reduce's layout)
         const int c = (blockIdx.x - (gridDim.x - post_blocks)) * 3 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1246,7 +1275,8 @@ __global__ __launch_bounds__(192) void k_schur_reduce(int nred, const int *__res
         const int rr = e / 9, cc = e - 9 * rr;
         T v = -s;
         if (hi == lo) v += V[(size_t)hi * 81 + e];
-        if (lam && hi == lo && rr == cc) v += *lam;
+        if constexpr (MARQ) { if (lam && hi == lo && rr == cc) v += ba_damp<true, T>(*lam, V[(size_t)hi * 81 + e], da); }
+        else if (lam && hi == lo && rr == cc) v += *lam;
         S[(size_t)(9 * lo + cc) * ld + 9 * hi + rr] = v;
     } else {
         const int cc = e - 81;
@@ -1259,9 +1289,10 @@ __global__ __launch_bounds__(192) void k_schur_reduce(int nred, const int *__res
 // After the (optional) all-reduce: add lambda to the diagonal, copy the summed g_c out of row D+1, clear the
 // augmented rows D+1.. and give the padding a unit diagonal so that the blocked LDL^T can run over whole tiles; arm the
 // solution vector with the hand-off sentinel.
-template <typename T>
+// MARQ (single shard, where S's diagonal is still V - s): fl(lambda clamp(V_qq)) instead of lambda.
+template <typename T, bool MARQ = false>
 __global__ __launch_bounds__(256) void k_post_reduce(int D, int Dp, int ld, const T *__restrict__ lam, T *__restrict__ S, T *__restrict__ gc_out,
-                                                     T *__restrict__ xarm)
+                                                     T *__restrict__ xarm, const T *__restrict__ V = nullptr, ba_damp_args<T> da = ba_damp_args<T>{})
 {
     // one wave per column, lane = row offset: the cleared rows of a column are contiguous (coalesced stores)
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1273,7 +1304,7 @@ __global__ __launch_bounds__(256) void k_post_reduce(int D, int Dp, int ld, cons
     }
     if (c < D) {
         if (lane == 0) {
-            col[c] += *lam;
+            col[c] += ba_damp<MARQ, T>(*lam, MARQ ? V[(size_t)(c / 9) * 81 + 10 * (c % 9)] : (T)0, da);
             gc_out[c] = col[D + 1]; // (this lane clears that entry below, in program order)
         }
         for (int rr = D + 1 + lane; rr < Dp; rr += 64) col[rr] = 0;
@@ -1360,28 +1391,32 @@ struct ba_cam_retract_args { int N; const void *cam, *dxc, *gc; void *cam_test, 
 // and PCG, roundoff for the dense QR kinds, whose reflectors mix the row's sqrt(lambda) in) is read as 0 by the point steps and written
 // back as 0 by the camera block; a fixed point's step is 0; fixed parameters of xTest are copies of x (the same bits, -0 included).
 struct ba_fix_args { const unsigned short *cmask; const unsigned char *pfix; };
-template <typename T, bool MASK = false>
+// MARQ (ba_solver_set_damping): the rho terms are x_q (d_q x_q + g_q) with d_q = fl(lambda clamp(diag_q)), the diagonal read from
+// U0[0, 3, 5] of the point and from V of the camera (dg.U0, dg.V: behind the arguments the identity instantiations always had).
+template <typename T> struct ba_damp_diag { const T *U0, *V; ba_damp_args<T> da; };
+template <typename T, bool MASK = false, bool MARQ = false>
 __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam, const T *__restrict__ dxc, const T *__restrict__ gc,
                                                 const T *__restrict__ lam, T *__restrict__ cam_test, T *__restrict__ scal, int dst, T *red,
-                                                const unsigned short *__restrict__ cmask = nullptr);
+                                                const unsigned short *__restrict__ cmask = nullptr, ba_damp_diag<T> dg = ba_damp_diag<T>{});
 
 // cr.N > 0: one more block at the end of the grid retracts the cameras (K8, below: a launch of its own otherwise); npart = the
 // number of point blocks = the row length of partial[2][npart].
-template <typename T, int LPP, bool MASK = false>
+template <typename T, int LPP, bool MASK = false, bool MARQ = false>
 __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,
                                                  const T *__restrict__ rec, const T *__restrict__ dinv, const T *__restrict__ tvec,
                                                  const T *__restrict__ tri, const T *__restrict__ dxc, const T *__restrict__ gp,
                                                  const T *__restrict__ pts, const T *__restrict__ lam, T *__restrict__ dxp, T *__restrict__ pts_test,
                                                  T *__restrict__ partial /* [2][npart] */, const int *__restrict__ pperm /* column permutation of the point's 3x3 block */,
-                                                 int npart, ba_cam_retract_args cr, ba_fix_args fx = ba_fix_args{})
+                                                 int npart, ba_cam_retract_args cr, ba_fix_args fx = ba_fix_args{},
+                                                 ba_damp_diag<T> dg = ba_damp_diag<T>{})
 {
     // LPP lanes per point: each lane forms Z_i^T dx_c for its observations (i = g, g + LPP, ...), a butterfly sum over
     // the group gives the point's 3-vector, lane 0 of the group finishes the 3x3 triangular solve.
     __shared__ T red[4];
     if (cr.N > 0 && (int)blockIdx.x == npart) {
         // (MASK: it zeroes the fixed rows of dx_c while the point blocks read it -- they mask what they read, so either value is fine)
-        ba_retract_cams<T, MASK>(cr.N, (const T *)cr.cam, (const T *)cr.dxc, (const T *)cr.gc, lam, (T *)cr.cam_test, (T *)cr.scal, cr.dst, red,
-                                 fx.cmask);
+        ba_retract_cams<T, MASK, MARQ>(cr.N, (const T *)cr.cam, (const T *)cr.dxc, (const T *)cr.gc, lam, (T *)cr.cam_test, (T *)cr.scal, cr.dst, red,
+                                       fx.cmask, dg);
         return;
     }
     const int gid = (blockIdx.x * 256 + threadIdx.x) / LPP, lg = threadIdx.x % LPP;
@@ -1422,6 +1457,11 @@ __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__
         pts_test[j] = pfixed ? pts[j] : pts[j] + x0;
         pts_test[(size_t)Ml + j] = pfixed ? pts[(size_t)Ml + j] : pts[(size_t)Ml + j] + x1;
         pts_test[2 * (size_t)Ml + j] = pfixed ? pts[2 * (size_t)Ml + j] : pts[2 * (size_t)Ml + j] + x2;
+        if constexpr (MARQ) {
+            const T d0 = ba_damp<true, T>(lambda, dg.U0[j], dg.da), d1 = ba_damp<true, T>(lambda, dg.U0[3 * (size_t)Ml + j], dg.da),
+                    d2 = ba_damp<true, T>(lambda, dg.U0[5 * (size_t)Ml + j], dg.da);
+            rho = x0 * (d0 * x0 + gp[j]) + x1 * (d1 * x1 + gp[(size_t)Ml + j]) + x2 * (d2 * x2 + gp[2 * (size_t)Ml + j]);
+        } else
         rho = x0 * (lambda * x0 + gp[j]) + x1 * (lambda * x1 + gp[(size_t)Ml + j]) + x2 * (lambda * x2 + gp[2 * (size_t)Ml + j]);
         dn = x0 * x0 + x1 * x1 + x2 * x2;
     }
@@ -1433,10 +1473,11 @@ __global__ __launch_bounds__(256) void k_backsub(int Ml, const int *__restrict__
 // ---- K8 (cameras): BAFunctor::update_params (src/Optimization/BAFunctor.h:311-332) -----------------------------
 // T += dT; R <- Rodrigues(d omega) R (identity when |d omega| <= 1e-6, src/MathUtils.h:66-82); f, k1, k2 += .
 // Single block (N <= a few thousand cameras); also the camera part of the rho / |dx|^2 sums -> scal[dst..dst+1].
-template <typename T, bool MASK>
+template <typename T, bool MASK, bool MARQ>
 __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam, const T *__restrict__ dxc,
                                                 const T *__restrict__ gc, const T *__restrict__ lam, T *__restrict__ cam_test,
-                                                T *__restrict__ scal, int dst, T *red, const unsigned short *__restrict__ cmask)
+                                                T *__restrict__ scal, int dst, T *red, const unsigned short *__restrict__ cmask,
+                                                ba_damp_diag<T> dg)
 {
     const T lambda = *lam;
     T rho = 0, dn = 0;
@@ -1450,7 +1491,8 @@ __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam
                 p[c] = 0;
                 ((T *)dxc)[9 * a + c] = 0; // (BA_GET_DX shows the step that was taken)
             }
-            rho += p[c] * (lambda * p[c] + gc[9 * a + c]);
+            if constexpr (MARQ) rho += p[c] * (ba_damp<true, T>(lambda, dg.V[(size_t)a * 81 + 10 * c], dg.da) * p[c] + gc[9 * a + c]);
+            else rho += p[c] * (lambda * p[c] + gc[9 * a + c]);
             dn += p[c] * p[c];
         }
         T R0[9];
@@ -1505,13 +1547,14 @@ __device__ __forceinline__ void ba_retract_cams(int N, const T *__restrict__ cam
     if (threadIdx.x == 0) { scal[dst] = rho; scal[dst + 1] = dn; }
 }
 
-template <typename T, bool MASK = false>
+template <typename T, bool MASK = false, bool MARQ = false>
 __global__ __launch_bounds__(256) void k_retract_cams(int N, const T *__restrict__ cam, const T *__restrict__ dxc,
                                                       const T *__restrict__ gc, const T *__restrict__ lam, T *__restrict__ cam_test,
-                                                      T *__restrict__ scal, int dst, const unsigned short *__restrict__ cmask = nullptr)
+                                                      T *__restrict__ scal, int dst, const unsigned short *__restrict__ cmask = nullptr,
+                                                      ba_damp_diag<T> dg = ba_damp_diag<T>{})
 {
     __shared__ T red[4];
-    ba_retract_cams<T, MASK>(N, cam, dxc, gc, lam, cam_test, scal, dst, red, cmask);
+    ba_retract_cams<T, MASK, MARQ>(N, cam, dxc, gc, lam, cam_test, scal, dst, red, cmask, dg);
 }
 
 // ---- a-8: step control on the device ---------------------------------------------------------------------------

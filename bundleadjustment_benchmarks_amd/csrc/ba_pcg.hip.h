@@ -178,10 +178,12 @@ __global__ __launch_bounds__(256) void k_pcg_prec_chunks(int ndchunks, const int
 
 // Per (camera, entry): the chunk partials summed in chunk order (k_cam_gram_reduce's order), then
 //   B_a = (V_a - s) + lambda I  into Bm (full 9 x 9, inverted in place by k_pcg_prec_inv),  rhs_a = g_c,a - s,  g_c copied to gc_out.
-template <typename T>
+// MARQ (ba_solver_set_damping): (V_a - s) + d with d = fl(lambda clamp(V_a,qq)) on the diagonal.
+template <typename T, bool MARQ = false>
 __global__ __launch_bounds__(256) void k_pcg_prec_reduce(int N, const int *__restrict__ cam_dchunk_ptr, const T *__restrict__ dslab,
                                                          const T *__restrict__ V, const T *__restrict__ gc, const T *__restrict__ lam,
-                                                         T *__restrict__ Bm, T *__restrict__ rhs, T *__restrict__ gc_out)
+                                                         T *__restrict__ Bm, T *__restrict__ rhs, T *__restrict__ gc_out,
+                                                         ba_damp_args<T> da = ba_damp_args<T>{})
 {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t a = idx / BA_SLAB;
@@ -208,8 +210,9 @@ __global__ __launch_bounds__(256) void k_pcg_prec_reduce(int N, const int *__res
         while ((rr + 1) * (rr + 2) / 2 <= e) rr++;
         const int cc = e - rr * (rr + 1) / 2;
         T v = -s;
-        v += V[a * 81 + 9 * rr + cc];
-        if (rr == cc) v += *lam;
+        const T vd = V[a * 81 + 9 * rr + cc];
+        v += vd;
+        if (rr == cc) v += ba_damp<MARQ, T>(*lam, vd, da);
         Bm[a * 81 + 9 * rr + cc] = v;
         Bm[a * 81 + 9 * cc + rr] = v;
     } else {
@@ -364,12 +367,13 @@ __global__ __launch_bounds__(256) void k_pcg_cam_chunks(int ndchunks, const int 
 
 // Camera pass, part 2, one thread per (camera, row): y_a,r = ((V_a + lambda I) v_a)_r - sum of the camera's chunk partials (chunk order);
 // the block partials of v'y (iteration) or |rhs - y|^2 (FINAL, y = S x) into part[blockIdx]
-template <typename T, bool FINAL>
+// MARQ (ba_solver_set_damping): (t + d v_r) - s with d = fl(lambda clamp(V_a,rr)).
+template <typename T, bool FINAL, bool MARQ = false>
 __global__ __launch_bounds__(256) void k_pcg_cam(int k, int N, const int *__restrict__ cam_dchunk_ptr, const T *__restrict__ slab,
                                                  const T *__restrict__ V, const T *__restrict__ lam, const T *__restrict__ z,
                                                  const T *__restrict__ p, const T *__restrict__ x, const T *__restrict__ rhs,
                                                  const double *__restrict__ part_rz, int gz, T *__restrict__ y, double *__restrict__ part,
-                                                 const ba_pcg_dev *__restrict__ pcg)
+                                                 const ba_pcg_dev *__restrict__ pcg, ba_damp_args<T> da = ba_damp_args<T>{})
 {
     __shared__ double red[4];
     T beta = 0;
@@ -403,7 +407,7 @@ __global__ __launch_bounds__(256) void k_pcg_cam(int k, int N, const int *__rest
             t += Va[q] * v;
             if (q == r) vr = v;
         }
-        const T yr = (t + *lam * vr) - s;
+        const T yr = (t + ba_damp<MARQ, T>(*lam, MARQ ? Va[r] : (T)0, da) * vr) - s;
         y[9 * a + r] = yr;
         if (FINAL) { const double d = (double)rhs[9 * a + r] - (double)yr; acc = d * d; }
         else acc = (double)vr * (double)yr;

@@ -180,11 +180,12 @@ __global__ __launch_bounds__(256) void k_prior(ba_prior_args<T> pa, int N, int M
 // lambda I, its gradient 0).  With a point prior its block is L'L + lambda I and its gradient -L'e: this kernel, behind k_backsub and
 // only when such points are listed, takes their step (U0 + lambda I) dx = gp by the 3 x 3 LDL^T of k_elim_chol, retracts them and
 // adds their rho and |dx|^2 terms to the partials of k_backsub's block 0.  One workgroup; a fixed point keeps k_backsub's copy.
-template <typename T, bool MASK = false>
-__global__ __launch_bounds__(256) void k_prior_lonely(int n, const int *__restrict__ ids, int Ml, const T *__restrict__ U0, const T *__restrict__ gp,
-                                                      const T *__restrict__ lam, const T *__restrict__ pts, T *__restrict__ dxp,
-                                                      T *__restrict__ pts_test, T *__restrict__ partial, int npart,
-                                                      const unsigned char *__restrict__ pfix)
+// MARQ (ba_solver_set_damping): the pivots and the rho terms take d_q = fl(lambda clamp(U0[0, 3, 5])) of the point instead of lambda.
+template <typename T, bool MASK, bool MARQ>
+__device__ __forceinline__ void ba_prior_lonely(int n, const int *__restrict__ ids, int Ml, const T *__restrict__ U0, const T *__restrict__ gp,
+                                                const T *__restrict__ lam, const T *__restrict__ pts, T *__restrict__ dxp,
+                                                T *__restrict__ pts_test, T *__restrict__ partial, int npart,
+                                                const unsigned char *__restrict__ pfix, ba_damp_args<T> da)
 {
     __shared__ T red[4];
     const size_t M = (size_t)Ml;
@@ -194,18 +195,37 @@ __global__ __launch_bounds__(256) void k_prior_lonely(int n, const int *__restri
         const int j = ids[q];
         if (MASK && pfix[j] != 0) continue;
         const T g0 = gp[j], g1 = gp[M + j], g2 = gp[2 * M + j];
-        const ba_chol3_t<T> c3 = ba_chol3<T>(U0[j], U0[M + j], U0[2 * M + j], U0[3 * M + j], U0[4 * M + j], U0[5 * M + j], g0, g1, g2, lambda);
+        T d0 = lambda, d1 = lambda, d2 = lambda;
+        if constexpr (MARQ) { d0 = ba_damp<true, T>(lambda, U0[j], da); d1 = ba_damp<true, T>(lambda, U0[3 * M + j], da); d2 = ba_damp<true, T>(lambda, U0[5 * M + j], da); }
+        const ba_chol3_t<T> c3 = ba_chol3<T>(U0[j], U0[M + j], U0[2 * M + j], U0[3 * M + j], U0[4 * M + j], U0[5 * M + j], g0, g1, g2, d0, d1, d2);
         const T x2 = c3.t2 * c3.i2;
         const T x1 = c3.t1 * c3.i1 - c3.l21 * x2;
         const T x0 = c3.t0 * c3.i0 - c3.l10 * x1 - c3.l20 * x2;
         dxp[j] = x0; dxp[M + j] = x1; dxp[2 * M + j] = x2;
         pts_test[j] = pts[j] + x0; pts_test[M + j] = pts[M + j] + x1; pts_test[2 * M + j] = pts[2 * M + j] + x2;
-        rho += x0 * (lambda * x0 + g0) + x1 * (lambda * x1 + g1) + x2 * (lambda * x2 + g2);
+        rho += x0 * (d0 * x0 + g0) + x1 * (d1 * x1 + g1) + x2 * (d2 * x2 + g2);
         dn += x0 * x0 + x1 * x1 + x2 * x2;
     }
     rho = block_reduce<T, false>(rho, red);
     dn = block_reduce<T, false>(dn, red);
     if (threadIdx.x == 0) { partial[0] = partial[0] + rho; partial[npart] = partial[npart] + dn; }
+}
+template <typename T, bool MASK = false>
+__global__ __launch_bounds__(256) void k_prior_lonely(int n, const int *__restrict__ ids, int Ml, const T *__restrict__ U0, const T *__restrict__ gp,
+                                                      const T *__restrict__ lam, const T *__restrict__ pts, T *__restrict__ dxp,
+                                                      T *__restrict__ pts_test, T *__restrict__ partial, int npart,
+                                                      const unsigned char *__restrict__ pfix)
+{
+    ba_prior_lonely<T, MASK, false>(n, ids, Ml, U0, gp, lam, pts, dxp, pts_test, partial, npart, pfix, ba_damp_args<T>{});
+}
+// (a kernel of its own: k_prior_lonely keeps its parameter list)
+template <typename T, bool MASK = false>
+__global__ __launch_bounds__(256) void k_prior_lonely_marq(int n, const int *__restrict__ ids, int Ml, const T *__restrict__ U0, const T *__restrict__ gp,
+                                                           const T *__restrict__ lam, const T *__restrict__ pts, T *__restrict__ dxp,
+                                                           T *__restrict__ pts_test, T *__restrict__ partial, int npart,
+                                                           const unsigned char *__restrict__ pfix, ba_damp_args<T> da)
+{
+    ba_prior_lonely<T, MASK, true>(n, ids, Ml, U0, gp, lam, pts, dxp, pts_test, partial, npart, pfix, da);
 }
 
 #endif

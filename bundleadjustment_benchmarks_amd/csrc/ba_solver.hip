@@ -105,6 +105,8 @@ struct SolverBase {
     virtual int selftest(int which) = 0;
     virtual int set_pcg(int max_iter, double rel_tol) = 0;
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
+    virtual int set_damping(int kind, double diag_min, double diag_max) = 0;
+    virtual int get_damping(int *kind, double *diag_min, double *diag_max) = 0;
     virtual int set_precond(int kind, int max_tree) = 0;
     virtual int precond_info(long long *out6, int *fallback_trees) = 0;
     virtual int set_shared(const int *group_of) = 0;
@@ -686,6 +688,10 @@ template <typename T> struct Solver final : SolverBase {
     void launch_eliminate()
     {
         if (chol_elim()) {
+            if (marq()) // (never the fused linearisation's records: they were made at lambda I)
+                hipLaunchKernelGGL((k_elim_chol<T, true>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
+                                   d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p, (const int *)nullptr, damp_args());
+            else
             hipLaunchKernelGGL((k_elim_chol<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
                                d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
                                fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
@@ -734,7 +740,11 @@ template <typename T> struct Solver final : SolverBase {
         }
         const int post_blocks = lamf ? (Dp + 2) / 3 : 0;
         const long long nthr = (long long)nred * BA_SLAB;
-        if (nred > 0)
+        if (nred > 0 && marq())
+            hipLaunchKernelGGL((k_schur_reduce<T, true>), dim3((unsigned)((nthr + 191) / 192) + post_blocks), dim3(192), 0, st, nred, d_red_pairs.p, D, ld,
+                               d_pair_hi.p, d_pair_lo.p, d_pair_chunk_ptr.p, d_slab.p, d_V.p, d_gc.p, d_S.p, lamf, post_blocks, Dp, d_gcg.p, d_dxc.p,
+                               damp_args());
+        else if (nred > 0)
             hipLaunchKernelGGL((k_schur_reduce<T>), dim3((unsigned)((nthr + 191) / 192) + post_blocks), dim3(192), 0, st, nred, d_red_pairs.p, D, ld,
                                d_pair_hi.p, d_pair_lo.p, d_pair_chunk_ptr.p, d_slab.p, d_V.p, d_gc.p, d_S.p, lamf, post_blocks, Dp, d_gcg.p, d_dxc.p);
         // every block of this S is written: the constraints' cross blocks join it here, for a trial and for the covariance alike
@@ -934,6 +944,10 @@ template <typename T> struct Solver final : SolverBase {
     void launch_post_reduce()
     {
         if (post_folded()) return;
+        if (marq()) // (single shard: the diagonal of V is the diagonal of J_c'J_c)
+            hipLaunchKernelGGL((k_post_reduce<T, true>), dim3((Dp + 3) / 4), dim3(256), 0, st, D, Dp, ld, d_scal.p + SC_LAMBDA, d_S.p, d_gcg.p, d_dxc.p,
+                               (const T *)d_V.p, damp_args());
+        else
         hipLaunchKernelGGL((k_post_reduce<T>), dim3((Dp + 3) / 4), dim3(256), 0, st, D, Dp, ld, d_scal.p + SC_LAMBDA, d_S.p, d_gcg.p, d_dxc.p);
     }
 
@@ -1249,6 +1263,10 @@ template <typename T> struct Solver final : SolverBase {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_prec_chunks<T>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p, d_obs_pt.p,
                                d_rec.p, d_tvec.p, Ml, d_dslab.p);
+        if (marq())
+            hipLaunchKernelGGL((k_pcg_prec_reduce<T, true>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
+                               d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, Bm ? Bm : d_pcg_M.p, rhs ? rhs : d_pcg_b.p, gc_out ? gc_out : d_gcg.p, damp_args());
+        else
         hipLaunchKernelGGL((k_pcg_prec_reduce<T>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
                            d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, Bm ? Bm : d_pcg_M.p, rhs ? rhs : d_pcg_b.p, gc_out ? gc_out : d_gcg.p);
     }
@@ -1279,6 +1297,10 @@ template <typename T> struct Solver final : SolverBase {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_cam_chunks<T, FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p,
                                d_obs_pt.p, d_rec.p, Ml, d_pcg_w.p, d_dslab.p, d_pcg.p);
+        if (marq())
+            hipLaunchKernelGGL((k_pcg_cam<T, FINAL, true>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
+                               d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gz(), d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p, damp_args());
+        else
         hipLaunchKernelGGL((k_pcg_cam<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
                            d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gz(), d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p);
         if (relposes()) // (+ the constraints' cross blocks: y and the block partials, directly behind)
@@ -1317,6 +1339,48 @@ template <typename T> struct Solver final : SolverBase {
         pcg_max_iter = max_iter; pcg_rel_tol = rel_tol;
         if (g_trial) { (void)hipGraphExecDestroy(g_trial); g_trial = nullptr; } // (captured with the old launch sequence)
         return BA_OK;
+    }
+    // ---- Marquardt's damping (ba_solver_set_damping) ------------------------------------------------------------
+    // lambda diag(J'J), clamped, instead of lambda I: the MARQ instantiations of the kernels that add lambda.  damp_off: inside the
+    // covariance calls, whose lambda keeps the meaning (J'J + lambda I)^-1.
+    int damp_kind = BA_DAMP_IDENTITY;
+    double damp_min = BA_DAMP_DIAG_MIN_DEFAULT, damp_max = BA_DAMP_DIAG_MAX_DEFAULT;
+    bool damp_off = false;
+    bool marq() const { return damp_kind == BA_DAMP_MARQUARDT && !damp_off; }
+    ba_damp_args<T> damp_args() const { return ba_damp_args<T>{(T)damp_min, (T)damp_max}; }
+    ba_damp_diag<T> damp_diag() const { return ba_damp_diag<T>{(const T *)d_U0.p, (const T *)d_V.p, damp_args()}; }
+    struct DampOff { // the identity instantiations for the length of a covariance call
+        bool &f, was;
+        explicit DampOff(bool &flag) : f(flag), was(flag) { f = true; }
+        ~DampOff() { f = was; }
+    };
+    int set_damping(int k, double dmin, double dmax) override
+    {
+        if (k == BA_DAMP_IDENTITY) {
+            if (damp_kind != k) drop_trial_graphs();
+            damp_kind = k;
+            return BA_OK;
+        }
+        if (k != BA_DAMP_MARQUARDT || !chol_elim() || sharded()) return BA_ERR_ARG;
+        if (dmin == 0) dmin = BA_DAMP_DIAG_MIN_DEFAULT;
+        if (dmax == 0) dmax = BA_DAMP_DIAG_MAX_DEFAULT;
+        const T tmin_ = (T)dmin, tmax_ = (T)dmax; // (the kernels see them in the solver's scalar type)
+        if (!(tmin_ > 0) || !(tmin_ <= tmax_) || !std::isfinite((double)tmin_) || !std::isfinite((double)tmax_)) return BA_ERR_ARG;
+        drop_trial_graphs(); // (captured with the other instantiations or other bounds)
+        damp_kind = k; damp_min = (double)tmin_; damp_max = (double)tmax_;
+        return BA_OK;
+    }
+    int get_damping(int *k, double *dmin, double *dmax) override
+    {
+        if (k) *k = damp_kind;
+        if (dmin) *dmin = damp_min;
+        if (dmax) *dmax = damp_max;
+        return BA_OK;
+    }
+    void drop_trial_graphs()
+    {
+        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl})
+            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
     }
     int pcg_stats(ba_pcg_stats *out, int reset) override
     {
@@ -1403,6 +1467,7 @@ template <typename T> struct Solver final : SolverBase {
             // refusals: host side, before any launch
             if ((kind != BA_CHOLESKY && kind != BA_QRCHOL) || sharded() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda))
                 return BA_ERR_ARG;
+            const DampOff identity(damp_off); // (this call's lambda means J'J + lambda I whatever ba_solver_set_damping holds)
             cov_valid = false;
             int rc;
             if (!d_cov.p) {
@@ -1647,6 +1712,7 @@ template <typename T> struct Solver final : SolverBase {
             if (!iterative() || sharded() || share_on() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
                 !(rel_tol >= 0 && rel_tol < 1) || !cov_request_ok(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov))
                 return BA_ERR_ARG;
+            const DampOff identity(damp_off); // (this call's lambda means J'J + lambda I whatever ba_solver_set_damping holds)
             int rc;
             McRun c;
             if ((rc = mc_begin(max_iter ? max_iter : pcg_max_iter, rel_tol != 0 ? rel_tol : pcg_rel_tol, c))) return rc;
@@ -1728,14 +1794,25 @@ template <typename T> struct Solver final : SolverBase {
         if (Ml > 0) { // the camera retraction rides as one more block at the end of the grid
             const ba_cam_retract_args cr{N, d_cam[0].p, d_dxc.p, d_gcg.p, d_cam[1].p, d_scal.p, (int)SC_RHO_C};
             // masked: the first reader of dx_c behind every kind's reduced solve forces the fixed rows (and fixed points) to a zero step
-            if (masked)
+            if (marq())
+                with_flag(masked, [&](auto MASKED) {
+                    hipLaunchKernelGGL((k_backsub<T, 8, MASKED(), true>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p,
+                                       d_tvec.p, d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB,
+                                       cr, ba_fix_args{d_cmask.p, d_pfix.p}, damp_diag());
+                });
+            else if (masked)
                 hipLaunchKernelGGL((k_backsub<T, 8, true>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
                                    d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr,
                                    ba_fix_args{d_cmask.p, d_pfix.p});
             else
                 hipLaunchKernelGGL((k_backsub<T, 8>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
                                    d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr);
-        } else if (masked) // (an empty shard keeps the zero partial sums written at creation)
+        } else if (marq())
+            with_flag(masked, [&](auto MASKED) {
+                hipLaunchKernelGGL((k_retract_cams<T, MASKED(), true>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
+                                   d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)d_cmask.p, damp_diag());
+            });
+        else if (masked) // (an empty shard keeps the zero partial sums written at creation)
             hipLaunchKernelGGL((k_retract_cams<T, true>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
                                d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)d_cmask.p);
         else
@@ -1848,7 +1925,7 @@ template <typename T> struct Solver final : SolverBase {
     // are not used -- every trial runs k_elim_chol on the U0 / gp that k_prior has completed -- while J, U0, gp and the energy partials
     // still come from the kernel a solver without priors runs (so priors without information leave its bits alone, fp32 included,
     // where the separate-launch linearisation does not reproduce the fused one's bits).
-    bool fused_records() const { return fuse && !priors(); }
+    bool fused_records() const { return fuse && !priors() && !marq(); } // (Marquardt: the records of a lambda I elimination are not the trial's)
     size_t prior_bytes() const
     {
         size_t n = bytes_of(d_part_pr) + bytes_of(d_pr_lonely);
@@ -2123,6 +2200,13 @@ template <typename T> struct Solver final : SolverBase {
         if ((rc = mark(EV_T4))) return rc;
         launch_backsub_retract();
         if (d_pr_lonely.n > 0) { // (points with a prior and no observation: none on a usual problem, no launch then)
+            if (marq())
+                with_flag(masked, [&](auto MASKED) {
+                    hipLaunchKernelGGL((k_prior_lonely_marq<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml,
+                                       (const T *)d_U0.p, (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p,
+                                       d_part_bs.p, gB, MASKED() ? (const unsigned char *)d_pfix.p : nullptr, damp_args());
+                });
+            else
             with_flag(masked, [&](auto MASKED) {
                 hipLaunchKernelGGL((k_prior_lonely<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
                                    (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p, d_part_bs.p, gB,
@@ -2475,11 +2559,12 @@ template <typename T> struct Solver final : SolverBase {
         else {
             // outer iteration 1: m_functor(x, r), df, JtRes, column norms; lambda0 = 1e-12 max diag J'J (:257-280; Cholesky.h:263-265);
             // MOREQR: 1e-6 * max column norm (BacktrackLevMarqMore.h:272-284)
+            // Marquardt's damping: lambda is dimensionless, lambda0 = lambda_init, and the diagonal's maximum is not asked for
             double e = 0, dmax = 0;
-            if ((rc = linearize(&e, &dmax))) return rc;
+            if ((rc = linearize(&e, damp_kind == BA_DAMP_MARQUARDT ? nullptr : &dmax))) return rc;
             h.energy = (T)e;
             h.fun_evals = 1;
-            h.lambda = kind == BA_MOREQR ? (T)(1e-6 * std::sqrt(dmax)) : (T)(1e-12 * dmax);
+            if (damp_kind != BA_DAMP_MARQUARDT) h.lambda = kind == BA_MOREQR ? (T)(1e-6 * std::sqrt(dmax)) : (T)(1e-12 * dmax);
         }
         if (!h.stop && dist_on() && (rc = dist_setup())) return rc; // (never inside a stream capture)
         if (!h.stop && sharded() && !dense_qr() && !d_pack.p && (rc = d_pack.alloc(pack_count() + 1))) return rc;
@@ -2889,6 +2974,14 @@ int ba_solver_preconditioner_info(ba_solver *s, long long *out6, int *fallback_t
 }
 int ba_solver_set_shared_intrinsics(ba_solver *s, const int *group_of) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_shared(group_of); }
 int ba_solver_shared_intrinsics_info(ba_solver *s, long long *out4) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->shared_info(out4); }
+int ba_solver_set_damping(ba_solver *s, int kind, double diag_min, double diag_max)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_damping(kind, diag_min, diag_max);
+}
+int ba_solver_get_damping(ba_solver *s, int *kind, double *diag_min, double *diag_max)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->get_damping(kind, diag_min, diag_max);
+}
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {

@@ -114,7 +114,7 @@ typedef struct {
     double lambda_max;           /* 1e10  */
     double lambda_decrease;      /* 10 (unused by the reference loop) */
     double lambda_increase_base; /* 2     */
-    double lambda_init;          /* 1e-3 (overwritten by 1e-12*max diag(J'J) at iteration 1) */
+    double lambda_init;          /* 1e-3 (overwritten by 1e-12*max diag(J'J) at iteration 1; BA_DAMP_MARQUARDT: lambda0 itself) */
     double tol_fun;              /* 1e-8  */
     int max_iter;                /* 1e6   */
     int max_fun_ev;              /* 1e6   */
@@ -553,7 +553,9 @@ int ba_intrinsics_group_plan(int N, const int *group_of, int chunk, int *n_group
  * group's mean and M is the preconditioner in force (all three kinds of ba_solver_set_preconditioner are legal).  Nothing else changes:
  * the linearisation, the point elimination, the back-substitution, the retraction and the LM control are the ungrouped solver's.
  * Damping: lambda P'P, that is lambda n_g on the shared parameter of a group of n_g cameras -- Marquardt's damping of the stacked
- * columns.  lambda0 = 1e-12 max diag J'J keeps its per-camera-column definition.
+ * columns.  lambda0 = 1e-12 max diag J'J keeps its per-camera-column definition.  Under BA_DAMP_MARQUARDT (ba_solver_set_damping) the
+ * same projected PCG implies lambda P'D P: lambda sum over the members a of D_a,q on a group's parameter q, Marquardt's damping of the
+ * unknown itself.
  * What a caller sees: BA_GET_DX rows 6..8 are bit-equal inside a group, so f, k1, k2 of the members stay bit-equal through
  * ba_solver_try_step, ba_solver_accept and ba_minimize; BA_GET_RHS returns Pi rhs; ba_solver_pcg_stats keeps its meaning with the
  * residual |Pi (rhs - S dx_c)| / |Pi rhs|; BA_GET_GRAD, BA_GET_JC and the energy are per camera as before.  Priors, relative poses,
@@ -575,6 +577,41 @@ int ba_intrinsics_group_plan(int N, const int *group_of, int chunk, int *n_group
 int ba_solver_set_shared_intrinsics(ba_solver *s, const int *group_of /* N, or NULL = none */);
 /* out4 = {groups, grouped cameras, cameras of the largest group, chunks}.  BA_ERR_ARG for another solver kind. */
 int ba_solver_shared_intrinsics_info(ba_solver *s, long long *out4);
+
+/* ---- Marquardt's damping (no reference counterpart; Ceres' min_lm_diagonal / max_lm_diagonal, Marquardt 1963) -- */
+
+/* BA_DAMP_IDENTITY: every trial solves (J'J + lambda I) dx = -J'e, as the reference does; a new solver's kind.
+ * BA_DAMP_MARQUARDT: a trial solves (J'J + lambda D) dx = -J'e, D diagonal, D_ii = min(max((J'J)_ii, diag_min), diag_max), J'J that of the
+ * last linearisation with every row and column of J in it: loss and weights, priors, the relative-pose blocks H_aa, the zero columns of
+ * masked parameters.  The point block is U_p + lambda D_p, the reduced system S = (V + lambda D_c) - sum Z diag(dinv) Z', and the model
+ * decrease the LM control divides by is rhoScale = dx'(lambda D dx + g).  lambda is dimensionless and the step is invariant under a
+ * change of units of any parameter (while no clamp bites).
+ * Rounding: d_i = fl(lambda clamp(diag_i)) in the solver's scalar type is formed first and then added exactly where lambda is added
+ * under BA_DAMP_IDENTITY, in the same order of additions.
+ * diag_min / diag_max: 0 = BA_DAMP_DIAG_MIN_DEFAULT / BA_DAMP_DIAG_MAX_DEFAULT; 0 < diag_min <= diag_max, both finite in the solver's
+ * scalar type.  A fixed parameter (ba_solver_set_constant) has diagonal 0, so D = diag_min there, its row of S is lambda diag_min alone,
+ * its step exactly 0 and its value keeps its bits.  A point nobody observes gets lambda diag_min and no step.
+ * BA_CHOLESKY and BA_ITERSCHUR, BA_F64 and BA_F32, shard_world == 1; combines with masks, losses, weights, priors, relative poses, every
+ * preconditioner and shared intrinsics.  With shared intrinsics the projected PCG is unchanged, so the damping of a group's parameter q
+ * is lambda P'D P = lambda sum over the members a of D_a,q -- Marquardt's damping of the unknown itself.
+ * A call takes effect at the next ba_solver_try_step / ba_minimize (the linearisation does not depend on the damping: no
+ * ba_solver_linearize needed), drops the captured trial graphs like ba_solver_set_pcg, and leaves a pending step acceptable.
+ * ba_minimize under BA_DAMP_MARQUARDT starts from lambda0 = lm.lambda_init (NOT overwritten by 1e-12 max diag J'J); lambda_min,
+ * lambda_max, the accept / rho / flat-line control and the table are unchanged.  ba_solver_time_phase uses the damping in force.  With
+ * BA_DAMP_MARQUARDT the fused linearisation's pre-made elimination records (made at lambda I) are not used: every trial runs the point
+ * elimination as a launch of its own, as with priors.
+ * NOT affected: ba_solver_covariance_compute / ba_solver_covariance_pcg keep their own lambda with the meaning (J'J + lambda I)^-1
+ * whatever damping is set.
+ * BA_ERR_ARG, the solver unchanged, for BA_DAMP_MARQUARDT only: BA_QRKIT, BA_QRCHOL, BA_QRSPQR and BA_MOREQR (they put sqrt(lambda) rows
+ * into the per-point QR and into J2bot: not built), a sharded solver (not built), bad bounds; and an unknown kind.
+ * ba_solver_set_damping(s, BA_DAMP_IDENTITY, ...) is legal for every solver kind and shard count (the bounds are ignored); a solver
+ * switched to Marquardt and back enqueues the launches and returns the bits of one that never was.  ba_solver_get_damping: every kind;
+ * any pointer may be NULL; the bounds are those of the last accepted BA_DAMP_MARQUARDT call (the defaults before one). */
+typedef enum { BA_DAMP_IDENTITY = 0, BA_DAMP_MARQUARDT = 1 } ba_damping_kind;
+#define BA_DAMP_DIAG_MIN_DEFAULT 1e-6 /* Ceres' min_lm_diagonal */
+#define BA_DAMP_DIAG_MAX_DEFAULT 1e32 /* Ceres' max_lm_diagonal */
+int ba_solver_set_damping(ba_solver *s, int kind, double diag_min, double diag_max);
+int ba_solver_get_damping(ba_solver *s, int *kind, double *diag_min, double *diag_max);
 
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);

@@ -120,8 +120,9 @@ template <bool MARQ, typename T> __device__ __forceinline__ T ba_damp(T lambda, 
 // The record (30 of its 32 scalars) leaves in one burst at the end: a record is two cache lines that only this thread writes, and
 // stores trickling out between the Jacobian loads left them half-written in L2 for a microsecond -- evicted partial lines made 96 MB
 // of HBM writes out of 58 MB at config 4 (rocprofv3 WRITE_SIZE).
-template <typename T> __device__ __forceinline__ void ba_chol_record(const T (&A)[18], const T (&B)[6], T l10, T l20, T l21, T i0, T i1, T i2,
-                                                                     T *__restrict__ rec_i)
+// ba_chol_z is the record's arithmetic, ba_chol_record the same followed by the owning thread's stores (the plain record path, below).
+template <typename T> __device__ __forceinline__ void ba_chol_z(const T (&A)[18], const T (&B)[6], T l10, T l20, T l21, T i0, T i1, T i2,
+                                                                T (&z)[BA_REC])
 {
 #pragma clang fp contract(off)
     T Bt[6];
@@ -131,7 +132,6 @@ template <typename T> __device__ __forceinline__ void ba_chol_record(const T (&A
         Bt[3 * rr + 1] = ba_fma(-l10, Bt[3 * rr], B[3 * rr + 1]);
         Bt[3 * rr + 2] = ba_fma(-l21, Bt[3 * rr + 1], ba_fma(-l20, Bt[3 * rr], B[3 * rr + 2]));
     }
-    T z[BA_REC];
 #pragma unroll
     for (int c = 0; c < 9; c++) {
         const T a0 = A[c], a1 = A[9 + c];
@@ -139,6 +139,12 @@ template <typename T> __device__ __forceinline__ void ba_chol_record(const T (&A
     }
     z[BA_REC_DINV] = i0; z[BA_REC_DINV + 1] = i1; z[BA_REC_DINV + 2] = i2;
     z[BA_REC_DINV + 3] = 0; z[BA_REC_DINV + 4] = 0;
+}
+template <typename T> __device__ __forceinline__ void ba_chol_record(const T (&A)[18], const T (&B)[6], T l10, T l20, T l21, T i0, T i1, T i2,
+                                                                     T *__restrict__ rec_i)
+{
+    T z[BA_REC];
+    ba_chol_z<T>(A, B, l10, l20, l21, i0, i1, i2, z);
     typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
     vec_t *o = (vec_t *)rec_i;
     constexpr int VW = 16 / sizeof(T);
@@ -148,6 +154,58 @@ template <typename T> __device__ __forceinline__ void ba_chol_record(const T (&A
 #pragma unroll
         for (int u = 0; u < VW; u++) v[u] = z[VW * q + u];
         o[q] = v;
+    }
+}
+
+// ---- the AoS records (rec: BA_REC scalars, JcA: 20) to memory a cache line at a time ------------------------------------
+// One thread owns one record, and storing it in 16-byte pieces puts every store instruction of a wavefront into 64 different cache
+// lines: the vector L1 writes through without merging, so L2 takes a 16-byte request per lane and piece (config 4: 6.4 M write
+// requests for the 119 MB the fused k_eval leaves).  A run of records is contiguous memory, so the wavefront stores it as that: the
+// owners put their records into an LDS image whose rows are the records, and lane i stores the 16 bytes at base + 16 i of every KiB
+// (2.0 M requests; the owner-per-record stores stay as BA_REC_PLAIN=1).  Only the way the bytes travel differs: no scalar, no pad.
+// LOADS of a record by its owner are left alone -- there the L1 does merge the pieces of a line (measured, `profiles/EXPERIMENTS.md`
+// section 7).  The image's row stride is an ODD number of 16-byte pieces (fp64: rec 17, JcA 11; fp32: rec 9, JcA 5), so the eight
+// lanes that one LDS cycle of a 16-byte store serves land on eight different groups of four banks.
+template <typename T, int R> struct ba_stage {
+    static constexpr int VW = 16 / sizeof(T); // scalars per piece
+    static constexpr int U = R / VW;          // pieces per record
+    static constexpr int S = (U | 1) * VW;    // scalars per row of the image
+    typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
+    static_assert(R % VW == 0, "a record is whole 16-byte pieces");
+};
+// LDS traffic between the lanes of ONE wavefront: the hardware keeps a wavefront's LDS instructions in order, the compiler must too.
+__device__ __forceinline__ void ba_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// Store the wavefront's n (<= 64, uniform) consecutive records, lane l owning record l (z; lanes >= n own none), to dst = the first
+// of them, in rounds of ROWS records through the wavefront's image img (ROWS rows).
+template <typename T, int R, int ROWS> __device__ __forceinline__ void ba_store_run(T *img, const T (&z)[R], int n, T *__restrict__ dst)
+{
+    typedef ba_stage<T, R> SG;
+    typedef typename SG::vec_t vec_t;
+    const int lane = threadIdx.x & 63;
+    for (int r0 = 0; r0 < n; r0 += ROWS) {
+        const int np = (n - r0 < ROWS ? n - r0 : ROWS) * SG::U;
+        ba_wave_sync(); // (the round before has been read out)
+        if (lane >= r0 && lane < r0 + ROWS && lane < n) {
+            vec_t *row = (vec_t *)(img + (lane - r0) * SG::S);
+#pragma unroll
+            for (int q = 0; q < SG::U; q++) {
+                vec_t v;
+#pragma unroll
+                for (int u = 0; u < SG::VW; u++) v[u] = z[SG::VW * q + u];
+                row[q] = v;
+            }
+        }
+        ba_wave_sync();
+        vec_t *o = (vec_t *)(dst + (size_t)r0 * R);
+#pragma unroll
+        for (int k = 0; k < (ROWS * SG::U + 63) / 64; k++) {
+            const int p = 64 * k + lane, row = p / SG::U;
+            if (p < np) o[p] = *(const vec_t *)(img + row * SG::S + (p - row * SG::U) * SG::VW);
+        }
     }
 }
 
@@ -164,7 +222,7 @@ template <typename T> __device__ __forceinline__ void ba_chol_record(const T (&A
 // J twice"):
 //   FUSE >= 1  U0_j = sum B^T B and g_p = -sum B^T r per point (k_point_prep's work: Jp and r are not read back), the per-observation
 //              terms meeting in LDS and summed by the point's first lane in observation order -- k_point_prep's order, its bits;
-//   FUSE == 2  (CHOLESKY) the point's 3 x 3 LDL^T at the lambda the step control has just left in scal[], t, and every observation's
+//   FUSE >= 2  (CHOLESKY) the point's 3 x 3 LDL^T at the lambda the step control has just left in scal[], t, and every observation's
 //              record Z_i -- k_elim_chol's work for the FIRST trial of the new outer iteration (Jc, Jp are not read back for it);
 //              *fresh = 1 tells that trial's k_elim_chol to leave at once.  Rejected trials re-run k_elim_chol from the stored J.
 template <typename T> struct ba_fuse_args {
@@ -229,6 +287,8 @@ template <typename T> __device__ __forceinline__ void ba_loss(int kind, T s, T s
 // MASK (ba_solver_set_constant): the columns of the parameters held constant are written as zeros -- Jc, JcA, Jp and the fused Aj / Bj
 // alike, so that everything built from J (g, U, V, S, the records, J2bot, max diag J'J) is the masked J's.  A separate instantiation:
 // the unmasked launch stays the kernel it was.
+// FUSE == 3 is FUSE == 2 with the records of JcA and rec leaving through LDS, a wavefront's run at a time (ba_store_run), behind the
+// point part -- the stores and nothing else; FUSE == 2 (BA_REC_PLAIN=1) is the kernel as it was.
 template <typename T, bool JAC, int FUSE = 0, bool SOA = true, bool MASK = false, bool MODEL = false>
 __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__restrict__ cam, const T *__restrict__ pts,
                                               const int *__restrict__ obs_cam, const int *__restrict__ obs_pt,
@@ -240,6 +300,7 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
 {
     static_assert(FUSE == 0 || JAC, "the fused point part belongs to the linearisation");
     static_assert(!MASK || JAC, "the mask is a property of the Jacobian");
+    constexpr bool COOP = FUSE == 3;
     __shared__ T red[4];
     if (go && *go == 0) return; // device-side LM control: the trial in front of this linearisation was rejected (uniform)
     const int b0 = fa.eb ? fa.eb[blockIdx.x] : (int)blockIdx.x * 256;
@@ -254,7 +315,7 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
         }
     }
     T e2 = 0;
-    T Aj[FUSE == 2 ? 18 : 1], Bj[FUSE > 0 ? 6 : 1], ej[2] = {0, 0};
+    T Aj[FUSE >= 2 ? 18 : 1], Bj[FUSE > 0 ? 6 : 1], ej[2] = {0, 0};
     int pj = 0;
     if (valid) {
         const int ci = obs_cam[i];
@@ -295,8 +356,10 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
             ej[0] = e0; ej[1] = e1;
             r[i] = e0;
             r[(size_t)K + i] = e1;
-            JcA[(size_t)i * 20 + 18] = e0;
-            JcA[(size_t)i * 20 + 19] = e1;
+            if (!COOP) {
+                JcA[(size_t)i * 20 + 18] = e0;
+                JcA[(size_t)i * 20 + 19] = e1;
+            }
             // -[XX - T]x  (poseDerivatives, BAFunctor.h:131-133; XX - T is formed as the reference forms it)
             const T v0 = XX0 - c[9], v1 = XX1 - c[10], v2 = XX2 - c[11];
             const T mJ[9] = {0, v2, -v1, -v2, 0, v0, v1, -v0, 0};
@@ -350,9 +413,11 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
                         Jc[(size_t)q * K + i] = t0;
                         Jc[(size_t)(9 + q) * K + i] = t1;
                     }
-                    JcA[(size_t)i * 20 + q] = t0; // gathered by camera in k_cam_gram: one 160-byte record per observation
-                    JcA[(size_t)i * 20 + 9 + q] = t1;
-                    if (FUSE == 2) { Aj[q] = t0; Aj[9 + q] = t1; }
+                    if (!COOP) {
+                        JcA[(size_t)i * 20 + q] = t0; // gathered by camera in k_cam_gram: one 160-byte record per observation
+                        JcA[(size_t)i * 20 + 9 + q] = t1;
+                    }
+                    if (FUSE >= 2) { Aj[q] = t0; Aj[9 + q] = t1; }
                 } else {
                     Jp[(size_t)(q - 9) * K + i] = t0;
                     Jp[(size_t)(q - 6) * K + i] = t1;
@@ -365,7 +430,7 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
     if (threadIdx.x == 0) partial[blockIdx.x] = e2;
     if constexpr (FUSE > 0) {
         // the point part: a point's observations are threads tl .. tl + k - 1 of this workgroup (point-aligned ranges)
-        __shared__ T cu[9][256];
+        __shared__ alignas(COOP ? 16 : alignof(T)) T cu[9][256];
         const int tl = threadIdx.x;
         {
             T u[9];
@@ -391,7 +456,7 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
             for (int q = 0; q < 6; q++) fa.U0[(size_t)q * Ml + pj] = U[q];
 #pragma unroll
             for (int q = 0; q < 3; q++) fa.gp[(size_t)q * Ml + pj] = g[q];
-            if (FUSE == 2) {
+            if (FUSE >= 2) {
                 const ba_chol3_t<T> c3 = ba_chol3<T>(U[0], U[1], U[2], U[3], U[4], U[5], g[0], g[1], g[2], *fa.lam);
                 const size_t M = (size_t)Ml;
                 fa.dinv[pj] = c3.i0; fa.dinv[M + pj] = c3.i1; fa.dinv[2 * M + pj] = c3.i2;
@@ -401,9 +466,28 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
                 pf[0][tl] = c3.l10; pf[1][tl] = c3.l20; pf[2][tl] = c3.l21; pf[3][tl] = c3.i0; pf[4][tl] = c3.i1; pf[5][tl] = c3.i2;
             }
         }
-        if constexpr (FUSE == 2) {
+        if constexpr (FUSE >= 2) {
             __syncthreads();
-            if (valid) {
+            if constexpr (COOP) {
+                // cu has had its last reader: a quarter of it is each wavefront's image, 16 records of either kind (576 scalars)
+                static_assert(16 * ba_stage<T, BA_REC>::S <= 9 * 256 / 4 && 16 * ba_stage<T, 20>::S <= 9 * 256 / 4, "a wavefront's image");
+                const int w0 = 64 * (tl >> 6), left = b1 - b0 - w0;
+                const int nw = __builtin_amdgcn_readfirstlane(left < 0 ? 0 : left > 64 ? 64 : left); // the wavefront's observations
+                T *img = &cu[0][0] + (tl >> 6) * (9 * 256 / 4);
+                {
+                    T a[20];
+#pragma unroll
+                    for (int q = 0; q < 18; q++) a[q] = Aj[q];
+                    a[18] = ej[0]; a[19] = ej[1];
+                    ba_store_run<T, 20, 16>(img, a, nw, JcA + (size_t)(b0 + w0) * 20);
+                }
+                T z[BA_REC];
+                if (valid) {
+                    const int fl = pfirst - b0; // the point's first lane
+                    ba_chol_z<T>(Aj, Bj, pf[0][fl], pf[1][fl], pf[2][fl], pf[3][fl], pf[4][fl], pf[5][fl], z);
+                }
+                ba_store_run<T, BA_REC, 16>(img, z, nw, fa.rec + (size_t)(b0 + w0) * BA_REC);
+            } else if (valid) {
                 const int fl = pfirst - b0; // the point's first lane
                 ba_chol_record<T>(Aj, Bj, pf[0][fl], pf[1][fl], pf[2][fl], pf[3][fl], pf[4][fl], pf[5][fl], fa.rec + (size_t)i * BA_REC);
             }
@@ -651,7 +735,11 @@ template <typename T> __global__ __launch_bounds__(256) void k_vdiag(int N, cons
 // recomputes its point's 3x3 LDL^T: 20 flops, cheaper than a second launch); the first observation of a point also
 // writes the per-point factors.
 // MARQ (ba_solver_set_damping): the pivots are damped by fl(lambda clamp(U0[0, 3, 5])) of the point instead of lambda.
-template <typename T, bool MARQ = false>
+// COOP: the wavefront's 64 consecutive records leave through LDS (ba_store_run); in a wavefront that holds observation K - 1 the lanes
+// past it stay for that, read what it reads and write nothing; a wavefront with no observation at all leaves (K = 0, an empty shard's
+// one workgroup, included: there is no observation K - 1 to read).
+// (JcA comes in by the owner's own 16-byte loads either way: the vector L1 merges those into whole lines, `profiles/EXPERIMENTS.md` section 7.)
+template <typename T, bool MARQ = false, bool COOP = false>
 __global__ __launch_bounds__(256) void k_elim_chol(int K, int Ml, const int *__restrict__ obs_pt, const int *__restrict__ pt_ptr,
                                                    const T *__restrict__ JcA /* [K][20] */, const T *__restrict__ Jp, const T *__restrict__ U0,
                                                    const T *__restrict__ gp, const T *__restrict__ lam, T *__restrict__ rec,
@@ -660,8 +748,12 @@ __global__ __launch_bounds__(256) void k_elim_chol(int K, int Ml, const int *__r
                                                    ba_damp_args<T> da = ba_damp_args<T>{})
 {
     if (fresh && *fresh != 0) return; // (uniform)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= K) return;
+    const int i0 = blockIdx.x * 256 + threadIdx.x;
+    if (!COOP && i0 >= K) return;
+    const int w0 = (int)blockIdx.x * 256 + (threadIdx.x & 192); // the wavefront's first observation
+    if (COOP && w0 >= K) return; // (uniform per wavefront)
+    const bool valid = i0 < K;
+    const int i = valid ? i0 : K - 1; // (COOP: a lane past K reads what the last observation reads)
     const T lambda = *lam;
     const int j = obs_pt[i];
     const size_t M = (size_t)Ml;
@@ -673,7 +765,7 @@ __global__ __launch_bounds__(256) void k_elim_chol(int K, int Ml, const int *__r
     } else
         c3 = ba_chol3<T>(U0[j], U0[M + j], U0[2 * M + j], U0[3 * M + j], U0[4 * M + j], U0[5 * M + j],
                          gp[j], gp[M + j], gp[2 * M + j], lambda);
-    if (i == pt_ptr[j]) {
+    if (valid && i == pt_ptr[j]) {
         dinv[j] = c3.i0; dinv[M + j] = c3.i1; dinv[2 * M + j] = c3.i2;
         tvec[j] = c3.t0; tvec[M + j] = c3.t1; tvec[2 * M + j] = c3.t2;
         tri[j] = 1; tri[M + j] = c3.l10; tri[2 * M + j] = c3.l20;
@@ -694,6 +786,13 @@ __global__ __launch_bounds__(256) void k_elim_chol(int K, int Ml, const int *__r
                 if (VW * q + u < 18) A[VW * q + u] = v[u];
         }
     }
+    if constexpr (COOP) {
+        __shared__ alignas(16) T stage[4][16 * ba_stage<T, BA_REC>::S]; // a wavefront's image: 16 records
+        const int nw = __builtin_amdgcn_readfirstlane(K - w0 > 64 ? 64 : K - w0); // the wavefront's observations (>= 1)
+        T z[BA_REC];
+        ba_chol_z<T>(A, B, c3.l10, c3.l20, c3.l21, c3.i0, c3.i1, c3.i2, z);
+        ba_store_run<T, BA_REC, 16>(stage[threadIdx.x >> 6], z, nw, rec + (size_t)w0 * BA_REC);
+    } else
     ba_chol_record<T>(A, B, c3.l10, c3.l20, c3.l21, c3.i0, c3.i1, c3.i2, rec + (size_t)i * BA_REC);
 }
 
@@ -1579,7 +1678,7 @@ template <typename T> struct ba_lm_dev {
     int timed;   // t_ctl / t_end describe the iteration just before this one (not the host-synchronous first linearisation)
     int prev_go; // ... and that iteration linearised
     int prev_code; // decision of the previous trial (accepted + 2 stop): what this shard put into the guard slot of the scalar all-reduce
-    int rec_fresh; // the fused linearisation (k_eval<T, true, 2>) has left the records of the NEXT trial: its k_elim_chol returns at once
+    int rec_fresh; // the fused linearisation (k_eval<T, true, FUSE >= 2>) has left the records of the NEXT trial: its k_elim_chol returns at once
 };
 // trial_ticks: t_ctl - previous t_end (elimination ... test energy); ctl_ticks_prev: the control segment (control, x = xTest,
 // linearisation) that preceded this trial; both < 0 when unknown

@@ -170,6 +170,7 @@ template <typename T> struct Solver final : SolverBase {
     int schur_window = 0;
     int nred = 0;
     bool no_fold = false; // BA_NO_FOLD (dev switch): every launch of its own again (A/B timing on one box)
+    bool rec_coop = true; // BA_REC_PLAIN (dev switch) clears it: every thread stores its own record of rec / JcA again (A/B, bit-equal)
     int schur_grid = 1, schur_wgs = 4 /* workgroups of k_schur_pairs per CU */, schur_bands = 8, schur_nband = 1;
     // state: x = d_cam[0], d_pts[0]; xTest = d_cam[1], d_pts[1] (x = xTest is a device-side copy, k_commit)
     // linearisation at x (r, J, J^T r, block diagonals, MOREQR's outer factors): one set
@@ -197,7 +198,7 @@ template <typename T> struct Solver final : SolverBase {
     // points by QR and then factors S = (Jc'Jc + lambda I) - sum Z Z' by LDL^T: 20x faster, but normal equations.
     bool more_qr_on = true;
     bool dense_qr() const { return kind == BA_QRKIT || kind == BA_QRSPQR || more_qr(); }
-    // CHOLESKY's linearisation (AoS camera records, fused k_eval<T, true, 2>) and point elimination (k_elim_chol): CHOLESKY and BA_ITERSCHUR
+    // CHOLESKY's linearisation (AoS camera records, fused k_eval<T, true, 3>, or 2 with the owners' stores) and point elimination (k_elim_chol): CHOLESKY and BA_ITERSCHUR
     bool chol_elim() const { return kind == BA_CHOLESKY || kind == BA_ITERSCHUR; }
     bool iterative() const { return kind == BA_ITERSCHUR; } // the reduced system by PCG (ba_pcg.hip.h): no S, no camera pairs
     bool more_qr() const { return kind == BA_MOREQR && more_qr_on; }
@@ -299,6 +300,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipHostGetDevicePointer((void **)&d_log, (void *)h_log, 0));
         use_graph = getenv("BA_NO_GRAPH") == nullptr;
         no_fold = getenv("BA_NO_FOLD") != nullptr;
+        rec_coop = getenv("BA_REC_PLAIN") == nullptr;
         dbg_qrcheck = getenv("BA_DBG_QRCHECK") != nullptr;
         dist_factor = getenv("BA_DIST_FACTOR") != nullptr && atoi(getenv("BA_DIST_FACTOR")) != 0;
         if (const char *wd = getenv("BA_WATCHDOG_S")) { const double v = atof(wd); if (v > 0) watchdog_s = v; }
@@ -574,27 +576,30 @@ template <typename T> struct Solver final : SolverBase {
                                          d_meas.p, tau2, d_r.p, d_Jc.p, d_Jp.p, d_JcA.p, d_part_e.p, go, commit ? d_cam[0].p : (T *)nullptr,              \
                                          commit ? d_pts[0].p : (T *)nullptr, fa)
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
+        // eval_coop: the fused CHOLESKY linearisation stores its records a wavefront's run at a time (FUSE = 3 in place of 2) -- except in
+        // fp32 on a problem of one round of workgroups, where it measured 2 % slower than the owners' stores (profiles/EXPERIMENTS.md, 7)
+        const bool eval_coop = rec_coop && !(sizeof(T) == 4 && gE <= 2 * num_cus);
         // masked: the same launches through the instantiations that zero the fixed columns (ba_solver_set_constant)
         // model(): the same launches again through the instantiations of the general measurement model (ba_solver_set_loss /
         // ba_solver_set_obs_weights); the reference's psi at 0.5 px without weights stays on the kernels it always ran
         if (model()) {
             if (!jac) BA_EVAL(false, 0, true, false, true);
             else if (masked) {
-                if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, true, true); else BA_EVAL(true, 0, false, true, true); }
+                if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false, true, true); else BA_EVAL(true, 2, false, true, true); } else BA_EVAL(true, 0, false, true, true); }
                 else if (fused && fuse) BA_EVAL(true, 1, true, true, true);
                 else BA_EVAL(true, 0, true, true, true);
             }
-            else if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, false, true); else BA_EVAL(true, 0, false, false, true); }
+            else if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false, false, true); else BA_EVAL(true, 2, false, false, true); } else BA_EVAL(true, 0, false, false, true); }
             else if (fused && fuse) BA_EVAL(true, 1, true, false, true);
             else BA_EVAL(true, 0, true, false, true);
         }
         else if (!jac) BA_EVAL(false, 0);
         else if (masked) {
-            if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false, true); else BA_EVAL(true, 0, false, true); }
+            if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false, true); else BA_EVAL(true, 2, false, true); } else BA_EVAL(true, 0, false, true); }
             else if (fused && fuse) BA_EVAL(true, 1, true, true);
             else BA_EVAL(true, 0, true, true);
         }
-        else if (chol_elim()) { if (fused && fuse) BA_EVAL(true, 2, false); else BA_EVAL(true, 0, false); }
+        else if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false); else BA_EVAL(true, 2, false); } else BA_EVAL(true, 0, false); }
         else if (fused && fuse) BA_EVAL(true, 1);
         else BA_EVAL(true, 0);
 #undef BA_EVAL
@@ -689,12 +694,16 @@ template <typename T> struct Solver final : SolverBase {
     {
         if (chol_elim()) {
             if (marq()) // (never the fused linearisation's records: they were made at lambda I)
-                hipLaunchKernelGGL((k_elim_chol<T, true>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
-                                   d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p, (const int *)nullptr, damp_args());
+                with_flag(rec_coop, [&](auto COOP) {
+                    hipLaunchKernelGGL((k_elim_chol<T, true, COOP()>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
+                                       d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p, (const int *)nullptr, damp_args());
+                });
             else
-            hipLaunchKernelGGL((k_elim_chol<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
-                               d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
-                               fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
+                with_flag(rec_coop, [&](auto COOP) {
+                    hipLaunchKernelGGL((k_elim_chol<T, false, COOP()>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
+                                       d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
+                                       fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
+                });
         } else if (kind == BA_MOREQR) {
             if (Kl > 0) // BacktrackLevMarqMore.h:297-345, the per-trial QR of [R ; sqrt(lambda) I]
                 hipLaunchKernelGGL((k_more_trial<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_scal.p + SC_LAMBDA,

@@ -51,6 +51,7 @@ EXPORTS = [
     "ba_solver_set_preconditioner", "ba_solver_preconditioner_info", "ba_relpose_forest_plan", "ba_problem_covisibility",
     "ba_intrinsics_group_plan", "ba_solver_set_shared_intrinsics", "ba_solver_shared_intrinsics_info",
     "ba_solver_set_damping", "ba_solver_get_damping",
+    "ba_solver_set_pcg_model_tol", "ba_solver_pcg_stop_stats",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -77,6 +78,11 @@ class Timing(C.Structure):
 class PCGStats(C.Structure):
     _fields_ = [("solves", C.c_longlong), ("total_iters", C.c_longlong), ("last_iters", C.c_int), ("last_converged", C.c_int),
                 ("last_rel_residual", C.c_double)]
+
+
+class PCGStopStats(C.Structure):
+    _fields_ = [("by_residual", C.c_longlong), ("by_model", C.c_longlong), ("at_cap", C.c_longlong), ("last_rule", C.c_int),
+                ("last_zeta", C.c_double), ("last_model", C.c_double)]
 
 
 class CovPCGStats(C.Structure):
@@ -144,6 +150,8 @@ def lib():
         L.ba_solver_recoveries.argtypes = [C.c_void_p]
         L.ba_solver_set_pcg.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.ba_solver_pcg_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ba_solver_set_pcg_model_tol.argtypes = [C.c_void_p, C.c_double]
+        L.ba_solver_pcg_stop_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ba_solver_set_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         L.ba_solver_get_damping.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
@@ -376,6 +384,11 @@ class Solver:
         """ITERSCHUR: at most max_iter PCG iterations per trial, stop at |r| <= rel_tol |rhs|."""
         _chk(lib().ba_solver_set_pcg(self._h, int(max_iter), float(rel_tol)), "ba_solver_set_pcg")
 
+    def set_pcg_model_tol(self, eta):
+        """ITERSCHUR: 0 < eta < 1 also stops a trial's PCG at iteration k >= 1 when zeta_k = k (s_k - s_{k-1}) / s_k < eta, with
+        s_k = x_k'(rhs + r_k) twice the model decrease of the iterate (truncated Newton; Ceres' eta = 0.1).  eta = 0 (a new solver's): off."""
+        _chk(lib().ba_solver_set_pcg_model_tol(self._h, float(eta)), "ba_solver_set_pcg_model_tol")
+
     def set_damping(self, kind, diag_min=0.0, diag_max=0.0):
         """DAMP_IDENTITY (a new solver's: lambda I) or DAMP_MARQUARDT: a trial solves (J'J + lambda D) dx = -J'e with
         D_ii = min(max((J'J)_ii, diag_min), diag_max); 0 = the library's defaults (1e-6, 1e32).  lambda is then dimensionless and
@@ -528,6 +541,13 @@ class Solver:
         st = PCGStats()
         _chk(lib().ba_solver_pcg_stats(self._h, C.byref(st), int(reset)), "ba_solver_pcg_stats")
         return {k: getattr(st, k) for k, _ in PCGStats._fields_}
+
+    def pcg_stop_stats(self, reset=False):
+        """ITERSCHUR with set_pcg_model_tol(eta > 0): solves ended by the residual rule, by the model rule and at the cap; the last
+        solve's rule (0 cap, 1 residual, 2 model), zeta_k and s_k at its final iterate."""
+        st = PCGStopStats()
+        _chk(lib().ba_solver_pcg_stop_stats(self._h, C.byref(st), int(reset)), "ba_solver_pcg_stop_stats")
+        return {k: getattr(st, k) for k, _ in PCGStopStats._fields_}
 
     def covariance(self, lam=0.0, cam_pairs=None, cams=None, points=None, compute=True):
         """Covariance blocks of the estimate at the last linearize(): Sigma = (J'J + lam I)^-1 on the free parameters, 0 for fixed ones

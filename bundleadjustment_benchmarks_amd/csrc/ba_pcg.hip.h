@@ -32,6 +32,12 @@
 // k_pcg_relpose, on z behind k_pcg_update (behind the forest's apply), and the partials of |rhs - y|^2 are formed again from the
 // projected y; the kernels of this file do not know about it.
 //
+// The model-decrease rule (ba_solver_set_pcg_model_tol; the kernels named *_q, launched instead of their namesakes
+// when eta > 0): k_pcg_update_q also leaves the block partials of s_{k+1} = x_{k+1}'(rhs + r_{k+1}) = -2 Q(x_{k+1}) in slot k + 1 of a
+// fourth list (part_s, gc entries per slot like |r|^2; slot 0 = 0 from k_pcg_start_q), and k_pcg_point_q, behind its residual test, stops
+// the solve at k >= 1 when zeta_k = k (s_k - s_{k-1}) / s_k < eta.  k_pcg_update and its _q namesake are one body (ba_pcg_update_body<..., QS>)
+// behind two entry points, the other three kernels of their own, so with eta = 0 a solve runs the kernels, the argument lists and the instructions it ran without the rule.
+//
 // What ba_pcg_multi.hip.h (the nine-column PCG of ba_solver_covariance_pcg) computes alike it takes from here: ba_chol9 / ba_chol9_inverse
 // (a B_a's Cholesky and inverse), ba_pcg_dir (the direction formed on the fly), ba_dot9 (a block row by a 9-vector).  The chunk-order
 // sums are spelled out per kernel: their tails differ on purpose, and the order of a sum is behaviour here.
@@ -50,6 +56,10 @@ struct ba_pcg_dev {
     long long solves, total_iters;
     int last_iters, last_converged;
     double last_rel_residual;
+    // the model-decrease rule (written by the *_q kernels alone)
+    int rule, last_rule; // what set `done`: 1 residual, 2 model (k_pcg_point_q); of the last counted solve, 0 = the cap
+    long long by_residual, by_model, at_cap;
+    double last_zeta, last_model;
 };
 
 #include "ba_pcg_forest.hip.h" /* (needs ba_pcg_dev) */
@@ -282,6 +292,24 @@ __global__ __launch_bounds__(256) void k_pcg_start(const double *__restrict__ pa
     if (threadIdx.x == 0) { pcg->bb = bb; pcg->done = 0; pcg->iters = 0; }
 }
 
+// with the model rule: s_0 = 0 into slot 0 of part_s as well
+__global__ __launch_bounds__(256) void k_pcg_start_q(const double *__restrict__ part_rr, int gc, ba_pcg_dev *__restrict__ pcg, double *__restrict__ part_s)
+{
+    __shared__ double red[4];
+    const double bb = ba_pcg_sum(part_rr, gc, red);
+    for (int i = threadIdx.x; i < gc; i += 256) part_s[i] = 0.0;
+    if (threadIdx.x == 0) { pcg->bb = bb; pcg->done = 0; pcg->iters = 0; pcg->rule = 0; }
+}
+
+// zeta_k = k (s_k - s_{k-1}) / s_k and s_k from the block partials of slots k and k - 1 (k >= 1); every block sums them itself
+__device__ __forceinline__ double ba_pcg_zeta(int k, const double *__restrict__ part_s, int gc, double *red, double *s_out)
+{
+    const double sk = ba_pcg_sum(part_s + (size_t)ba_pcg_slot(k) * gc, gc, red);
+    const double sm = ba_pcg_sum(part_s + (size_t)ba_pcg_slot(k + 2) * gc, gc, red);
+    *s_out = sk;
+    return (double)k * (sk - sm) / sk;
+}
+
 // ---- per iteration k (FINAL: the product S x behind the last iteration) -----------------------------------------------------------------
 // beta_k = (r_k'z_k) / (r_{k-1}'z_{k-1}) from the block partials (0 at k = 0); every block sums them itself
 __device__ __forceinline__ double ba_pcg_beta(int k, const double *__restrict__ part_rz, int gz, double *red)
@@ -322,6 +350,54 @@ __global__ __launch_bounds__(256) void k_pcg_point(int k, int Ml, const int *__r
 #pragma unroll
         for (int c = 0; c < 9; c++) {
             const T v = ba_pcg_dir<FINAL>(x, z, p, beta, c0 + c);
+            s0 += Z[3 * c] * v; s1 += Z[3 * c + 1] * v; s2 += Z[3 * c + 2] * v;
+        }
+    }
+    s0 = group_sum<T, LPP>(s0); s1 = group_sum<T, LPP>(s1); s2 = group_sum<T, LPP>(s2);
+    if (ok && lg == 0) {
+        const size_t j = (size_t)gid, M = (size_t)Ml;
+        const bool empty = b == e; // (no record ever wrote this point's dinv)
+        w[j] = empty ? (T)0 : dinv[j] * s0;
+        w[M + j] = empty ? (T)0 : dinv[M + j] * s1;
+        w[2 * M + j] = empty ? (T)0 : dinv[2 * M + j] * s2;
+    }
+}
+// k_pcg_point<T, LPP, false> with the model rule behind the residual's.  A kernel of its own and not one body behind two entry points like
+// k_pcg_update: inlined into two kernels the fp64 gather came out with another base address for its record loads, and the kernels of a
+// solve without the rule are to stay the instructions they were.
+template <typename T, int LPP>
+__global__ __launch_bounds__(256) void k_pcg_point_q(int k, int Ml, const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,
+                                                     const T *__restrict__ rec, const T *__restrict__ dinv, const T *__restrict__ z,
+                                                     const T *__restrict__ p, const double *__restrict__ part_rz,
+                                                     const double *__restrict__ part_rr, int gc, int gz, double tol2, ba_pcg_dev *__restrict__ pcg,
+                                                     T *__restrict__ w, double eta, const double *__restrict__ part_s)
+{
+    __shared__ double red[4];
+    if (pcg->done) return; // (uniform)
+    const double rr = ba_pcg_sum(part_rr + (size_t)ba_pcg_slot(k) * gc, gc, red);
+    if (rr <= tol2 * pcg->bb) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { pcg->done = 1; pcg->iters = k; pcg->rule = 1; }
+        return;
+    }
+    if (k >= 1) { // zeta_k < eta: the model has stopped decreasing (s_k <= 0 or not finite: no verdict); every block sees the same sums
+        double sk;
+        const double zeta = ba_pcg_zeta(k, part_s, gc, red, &sk);
+        if (sk > 0 && sk < INFINITY && zeta < eta) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) { pcg->done = 1; pcg->iters = k; pcg->rule = 2; }
+            return;
+        }
+    }
+    const T beta = (T)ba_pcg_beta(k, part_rz, gz, red);
+    const int gid = (blockIdx.x * 256 + threadIdx.x) / LPP, lg = threadIdx.x % LPP;
+    const bool ok = gid < Ml;
+    const int b = ok ? pt_ptr[gid] : 0, e = ok ? pt_ptr[gid + 1] : 0;
+    T s0 = 0, s1 = 0, s2 = 0;
+    for (int i = b + lg; i < e; i += LPP) {
+        const T *Z = rec + (size_t)i * BA_REC;
+        const size_t c0 = 9 * (size_t)obs_cam[i];
+#pragma unroll
+        for (int c = 0; c < 9; c++) {
+            const T v = ba_pcg_dir<false>((const T *)nullptr, z, p, beta, c0 + c);
             s0 += Z[3 * c] * v; s1 += Z[3 * c + 1] * v; s2 += Z[3 * c + 2] * v;
         }
     }
@@ -450,11 +526,13 @@ __global__ __launch_bounds__(256) void k_pcg_relpose(int k, int N, ba_relpose_cs
 
 // Per camera (one thread): alpha_k = r_k'z_k / p_k'S p_k; x += alpha p_k; r -= alpha S p_k; p <- p_k; z = M^-1 r; the block partials of
 // r_{k+1}'z_{k+1} and |r_{k+1}|^2 into slot k + 1
-template <typename T, bool FOREST = false>
-__global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__restrict__ Minv, const T *__restrict__ y, T *__restrict__ z,
-                                                    T *__restrict__ p, T *__restrict__ x, T *__restrict__ r, double *__restrict__ part_rz,
-                                                    double *__restrict__ part_rr, const double *__restrict__ part_py, int gc, int gz, int gq,
-                                                    const ba_pcg_dev *__restrict__ pcg, const unsigned char *__restrict__ in_tree)
+// (QS, k_pcg_update_q: also the block partials of s_{k+1} = x_{k+1}'(rhs + r_{k+1}), from the values just written, into slot k + 1)
+template <typename T, bool FOREST, bool QS>
+__device__ __forceinline__ void ba_pcg_update_body(int k, int N, const T *__restrict__ Minv, const T *__restrict__ y, T *__restrict__ z,
+                                                   T *__restrict__ p, T *__restrict__ x, T *__restrict__ r, double *__restrict__ part_rz,
+                                                   double *__restrict__ part_rr, const double *__restrict__ part_py, int gc, int gz, int gq,
+                                                   const ba_pcg_dev *__restrict__ pcg, const unsigned char *__restrict__ in_tree,
+                                                   const T *__restrict__ rhs, double *__restrict__ part_s)
 {
     __shared__ double red[4];
     if (pcg->done) return;
@@ -463,17 +541,19 @@ __global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__res
     const double py = ba_pcg_sum(part_py, gq, red);
     const T alpha = (T)(rzk / py);
     const int a = blockIdx.x * 256 + threadIdx.x;
-    double rz = 0, rr = 0;
+    double rz = 0, rr = 0, sx = 0;
     if (a < N) {
         const size_t o = 9 * (size_t)a;
         T rv[9];
 #pragma unroll
         for (int q = 0; q < 9; q++) {
             const T pv = z[o + q] + beta * p[o + q];
-            x[o + q] += alpha * pv;
+            const T xv = x[o + q] + alpha * pv;
+            x[o + q] = xv;
             p[o + q] = pv;
             rv[q] = r[o + q] - alpha * y[o + q];
             r[o + q] = rv[q];
+            if (QS) sx += (double)xv * ((double)rhs[o + q] + (double)rv[q]);
         }
         const T *Mi = Minv + (size_t)a * 81;
         const bool tree = FOREST && in_tree[a]; // (z and r'z of this camera: k_pcg_forest_apply, directly behind)
@@ -495,6 +575,27 @@ __global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__res
         part_rz[(size_t)ba_pcg_slot(k + 1) * gz + blockIdx.x] = rz;
         part_rr[(size_t)ba_pcg_slot(k + 1) * gc + blockIdx.x] = rr;
     }
+    if (QS) {
+        sx = block_reduce<double, false>(sx, red);
+        if (threadIdx.x == 0) part_s[(size_t)ba_pcg_slot(k + 1) * gc + blockIdx.x] = sx;
+    }
+}
+template <typename T, bool FOREST = false>
+__global__ __launch_bounds__(256) void k_pcg_update(int k, int N, const T *__restrict__ Minv, const T *__restrict__ y, T *__restrict__ z,
+                                                    T *__restrict__ p, T *__restrict__ x, T *__restrict__ r, double *__restrict__ part_rz,
+                                                    double *__restrict__ part_rr, const double *__restrict__ part_py, int gc, int gz, int gq,
+                                                    const ba_pcg_dev *__restrict__ pcg, const unsigned char *__restrict__ in_tree)
+{
+    ba_pcg_update_body<T, FOREST, false>(k, N, Minv, y, z, p, x, r, part_rz, part_rr, part_py, gc, gz, gq, pcg, in_tree, nullptr, nullptr);
+}
+template <typename T, bool FOREST = false>
+__global__ __launch_bounds__(256) void k_pcg_update_q(int k, int N, const T *__restrict__ Minv, const T *__restrict__ y, T *__restrict__ z,
+                                                      T *__restrict__ p, T *__restrict__ x, T *__restrict__ r, double *__restrict__ part_rz,
+                                                      double *__restrict__ part_rr, const double *__restrict__ part_py, int gc, int gz, int gq,
+                                                      const ba_pcg_dev *__restrict__ pcg, const unsigned char *__restrict__ in_tree,
+                                                      const T *__restrict__ rhs, double *__restrict__ part_s)
+{
+    ba_pcg_update_body<T, FOREST, true>(k, N, Minv, y, z, p, x, r, part_rz, part_rr, part_py, gc, gz, gq, pcg, in_tree, rhs, part_s);
 }
 
 // One block, behind the product S x: iterations used, convergence, |rhs - S x| / |rhs|.  Counted unless `skip` is set (a trial that
@@ -516,6 +617,35 @@ __global__ __launch_bounds__(256) void k_pcg_finish(int max_iter, const double *
     pcg->last_iters = iters;
     pcg->last_converged = conv;
     pcg->last_rel_residual = bb > 0 ? sqrt(res / bb) : 0.0;
+}
+// with the model rule: also which rule ended the solve (at the cap: the residual's when |r_max_iter| meets it, else none), zeta and s of
+// the final iterate, and the three counters -- counted as above
+__global__ __launch_bounds__(256) void k_pcg_finish_q(int max_iter, const double *__restrict__ part_rr, int gc, const double *__restrict__ part_res,
+                                                      int gq, double tol2, ba_pcg_dev *__restrict__ pcg, const int *__restrict__ skip,
+                                                      const double *__restrict__ part_s)
+{
+    __shared__ double red[4];
+    const double rr = ba_pcg_sum(part_rr + (size_t)ba_pcg_slot(max_iter) * gc, gc, red);
+    const double res = ba_pcg_sum(part_res, gq, red);
+    const bool done = pcg->done != 0; // (uniform: nothing writes it behind the iterations)
+    const int iters = done ? pcg->iters : max_iter;
+    double sk = 0, zeta = 0;
+    if (iters >= 1) zeta = ba_pcg_zeta(iters, part_s, gc, red, &sk);
+    if (threadIdx.x != 0) return;
+    const double bb = pcg->bb;
+    const int rule = done ? pcg->rule : rr <= tol2 * bb ? 1 : 0;
+    if (skip && *skip) return;
+    pcg->solves += 1;
+    pcg->total_iters += iters;
+    pcg->last_iters = iters;
+    pcg->last_converged = rule != 0;
+    pcg->last_rel_residual = bb > 0 ? sqrt(res / bb) : 0.0;
+    pcg->last_rule = rule;
+    pcg->last_zeta = zeta;
+    pcg->last_model = sk;
+    if (rule == 1) pcg->by_residual += 1;
+    else if (rule == 2) pcg->by_model += 1;
+    else pcg->at_cap += 1;
 }
 
 #endif

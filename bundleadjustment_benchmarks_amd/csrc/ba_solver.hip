@@ -105,6 +105,8 @@ struct SolverBase {
     virtual int selftest(int which) = 0;
     virtual int set_pcg(int max_iter, double rel_tol) = 0;
     virtual int pcg_stats(ba_pcg_stats *out, int reset) = 0;
+    virtual int set_pcg_model_tol(double eta) = 0;
+    virtual int pcg_stop_stats(ba_pcg_stop_stats *out, int reset) = 0;
     virtual int set_damping(int kind, double diag_min, double diag_max) = 0;
     virtual int get_damping(int *kind, double *diag_min, double *diag_max) = 0;
     virtual int set_precond(int kind, int max_tree) = 0;
@@ -967,6 +969,9 @@ template <typename T> struct Solver final : SolverBase {
     int pcg_gc = 1, pcg_gq = 1; // blocks of the per-camera and per-(camera, row) launches
     int pcg_max_iter = BA_PCG_MAX_ITER_DEFAULT;
     double pcg_rel_tol = BA_PCG_REL_TOL_DEFAULT;
+    double pcg_eta = 0;            // ba_solver_set_pcg_model_tol: > 0 launches the *_q kernels (ba_pcg.hip.h)
+    DevBuf<double> d_pcg_part_s;   // their block partials of x'(rhs + r) [3][gc], allocated by the first eta > 0
+    bool qstop_on() const { return pcg_eta > 0; }
     // (with a forest the list of r'z is longer by one partial per tree and the four lists live in the forest's own buffer)
     int pcg_gz() const { return pcg_gc + (forest_on() ? fo.nparts() : 0); }
     double *pcg_part_rz() const { return forest_on() ? fo.part.p : d_pcg_part.p; }
@@ -1294,6 +1299,8 @@ template <typename T> struct Solver final : SolverBase {
         });
         if (forest) launch_forest_apply<true>(pcg_part_rz() + pcg_gc);
         if (share_on()) launch_share<false>(d_pcg_z.p); // z_0 <- Pi z_0 (r_0'z_0 of the unprojected z_0 is r_0'(Pi z_0): r_0 is in range(Pi))
+        if (qstop_on()) hipLaunchKernelGGL(k_pcg_start_q, dim3(1), dim3(256), 0, st, pcg_part_rr(), pcg_gc, d_pcg.p, d_pcg_part_s.p);
+        else
         hipLaunchKernelGGL(k_pcg_start, dim3(1), dim3(256), 0, st, pcg_part_rr(), pcg_gc, d_pcg.p);
     }
     // y = S v: the point pass, then the camera pass (chunk partials in d_dslab, then per camera)
@@ -1301,8 +1308,15 @@ template <typename T> struct Solver final : SolverBase {
     {
         const T *lam = d_scal.p + SC_LAMBDA;
         if (Ml > 0)
+            with_flag(!FINAL && qstop_on(), [&](auto QS) { // (the model rule sits behind the residual's, at the head of an iteration)
+                if constexpr (decltype(QS)::value)
+                    hipLaunchKernelGGL((k_pcg_point_q<T, 8>), dim3((unsigned)(((size_t)Ml * 8 + 255) / 256)), dim3(256), 0, st, k, Ml, d_pt_ptr.p, d_obs_cam.p,
+                                       d_rec.p, d_dinv.p, d_pcg_z.p, d_pcg_p.p, pcg_part_rz(), pcg_part_rr(), pcg_gc, pcg_gz(), tol2, d_pcg.p, d_pcg_w.p,
+                                       pcg_eta, (const double *)d_pcg_part_s.p);
+                else
             hipLaunchKernelGGL((k_pcg_point<T, 8, FINAL>), dim3((unsigned)(((size_t)Ml * 8 + 255) / 256)), dim3(256), 0, st, k, Ml, d_pt_ptr.p, d_obs_cam.p,
                                d_rec.p, d_dinv.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p, pcg_part_rz(), pcg_part_rr(), pcg_gc, pcg_gz(), tol2, d_pcg.p, d_pcg_w.p);
+            });
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_cam_chunks<T, FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p,
                                d_obs_pt.p, d_rec.p, Ml, d_pcg_w.p, d_dslab.p, d_pcg.p);
@@ -1330,6 +1344,11 @@ template <typename T> struct Solver final : SolverBase {
         for (int k = 0; k < pcg_max_iter; k++) {
             launch_pcg_matvec<false>(k, tol2);
             with_flag(forest_on(), [&](auto FOREST) {
+                if (qstop_on())
+                    hipLaunchKernelGGL((k_pcg_update_q<T, FOREST()>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p,
+                                       d_dxc.p, d_pcg_r.p, pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p,
+                                       FOREST() ? (const unsigned char *)fo.in_tree.p : nullptr, (const T *)d_pcg_b.p, d_pcg_part_s.p);
+                else
                 hipLaunchKernelGGL((k_pcg_update<T, FOREST()>), dim3(pcg_gc), dim3(256), 0, st, k, N, d_pcg_M.p, d_pcg_y.p, d_pcg_z.p, d_pcg_p.p, d_dxc.p,
                                    d_pcg_r.p, pcg_part_rz(), pcg_part_rr(), pcg_part_py(), pcg_gc, pcg_gz(), pcg_gq, d_pcg.p,
                                    FOREST() ? (const unsigned char *)fo.in_tree.p : nullptr);
@@ -1339,6 +1358,10 @@ template <typename T> struct Solver final : SolverBase {
         }
         launch_pcg_matvec<true>(pcg_max_iter, tol2);
         // (a trial ba_minimize enqueued behind the row that ended the run is not counted: lm->stop is already set when it runs)
+        if (qstop_on())
+            hipLaunchKernelGGL(k_pcg_finish_q, dim3(1), dim3(256), 0, st, pcg_max_iter, pcg_part_rr(), pcg_gc, pcg_part_res(), pcg_gq, tol2, d_pcg.p,
+                               step_level ? (const int *)nullptr : (const int *)&d_lm.p->stop, (const double *)d_pcg_part_s.p);
+        else
         hipLaunchKernelGGL(k_pcg_finish, dim3(1), dim3(256), 0, st, pcg_max_iter, pcg_part_rr(), pcg_gc, pcg_part_res(), pcg_gq, tol2, d_pcg.p,
                            step_level ? (const int *)nullptr : (const int *)&d_lm.p->stop);
     }
@@ -1347,6 +1370,37 @@ template <typename T> struct Solver final : SolverBase {
         if (!iterative() || max_iter < 1 || !(rel_tol > 0 && rel_tol < 1)) return BA_ERR_ARG;
         pcg_max_iter = max_iter; pcg_rel_tol = rel_tol;
         if (g_trial) { (void)hipGraphExecDestroy(g_trial); g_trial = nullptr; } // (captured with the old launch sequence)
+        return BA_OK;
+    }
+    // the model-decrease rule of the solve: the *_q kernels while eta > 0, the kernels of a solver that never had
+    // the rule at eta = 0.  The linearisation and a pending step do not depend on it.
+    int set_pcg_model_tol(double eta) override
+    {
+        if (!iterative() || !(eta >= 0 && eta < 1)) return BA_ERR_ARG; // (a NaN fails both comparisons)
+        if (eta > 0 && !d_pcg_part_s.p) {
+            HIPCHK(hipStreamSynchronize(st));
+            int rc;
+            if ((rc = d_pcg_part_s.alloc((size_t)3 * pcg_gc))) { d_pcg_part_s.release(); return rc; }
+            HIPCHK(hipMemset(d_pcg_part_s.p, 0, sizeof(double) * d_pcg_part_s.n));
+        }
+        if (eta != pcg_eta && g_trial) { (void)hipGraphExecDestroy(g_trial); g_trial = nullptr; } // (captured with the other kernels or eta)
+        pcg_eta = eta;
+        return BA_OK;
+    }
+    int pcg_stop_stats(ba_pcg_stop_stats *out, int reset) override
+    {
+        if (!iterative()) return BA_ERR_ARG;
+        ba_pcg_dev h{};
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(&h, d_pcg.p, sizeof h, hipMemcpyDeviceToHost));
+        if (out) {
+            out->by_residual = h.by_residual; out->by_model = h.by_model; out->at_cap = h.at_cap;
+            out->last_rule = h.last_rule; out->last_zeta = h.last_zeta; out->last_model = h.last_model;
+        }
+        if (reset) {
+            h.by_residual = 0; h.by_model = 0; h.at_cap = 0; h.last_rule = 0; h.last_zeta = 0; h.last_model = 0;
+            HIPCHK(hipMemcpy(d_pcg.p, &h, sizeof h, hipMemcpyHostToDevice));
+        }
         return BA_OK;
     }
     // ---- Marquardt's damping (ba_solver_set_damping) ------------------------------------------------------------
@@ -1420,7 +1474,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_q1lam, &d_mQl, &d_mQR, &d_R22, &d_qB, &d_qAcopy, &d_dbgr, &d_dbg2, &d_stage, &d_pcg_M, &d_pcg_b, &d_pcg_r,
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
-        return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg) + bytes_of(d_cmask) +
+        return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg_part_s) + bytes_of(d_pcg) + bytes_of(d_cmask) +
                bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
     }
 
@@ -2992,6 +3046,11 @@ int ba_solver_get_damping(ba_solver *s, int *kind, double *diag_min, double *dia
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->get_damping(kind, diag_min, diag_max);
 }
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stats(out, reset); }
+int ba_solver_set_pcg_model_tol(ba_solver *s, double eta) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_pcg_model_tol(eta); }
+int ba_solver_pcg_stop_stats(ba_solver *s, ba_pcg_stop_stats *out, int reset)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->pcg_stop_stats(out, reset);
+}
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes)
 {
     if (!s || !bytes) return BA_ERR_ARG;

@@ -54,8 +54,10 @@ enum {
  * then the reduced camera system S dx_c = rhs -- the same S and rhs CHOLESKY assembles, lambda on the diagonal -- solved by block-Jacobi
  * preconditioned conjugate gradients from dx_c = 0, with products by S computed from the elimination's records and S never formed.  A
  * step is inexact: the iteration stops at |rhs - S dx_c| <= rel_tol |rhs| (recurrence residual) or after max_iter iterations
- * (ba_solver_set_pcg; defaults BA_PCG_MAX_ITER_DEFAULT, BA_PCG_REL_TOL_DEFAULT).  The LM loop is CHOLESKY's; its rhoScale
- * dx'(lambda dx + g) is then an approximation of the model decrease.  Device memory O(K + 81 N) (ba_solver_device_bytes), no D x D
+ * (ba_solver_set_pcg; defaults BA_PCG_MAX_ITER_DEFAULT, BA_PCG_REL_TOL_DEFAULT), or, when asked for, once the model decrease has
+ * converged (ba_solver_set_pcg_model_tol).  The LM loop is CHOLESKY's; its rhoScale dx'(lambda dx + g) is the model decrease of the
+ * truncated step up to rounding, since an early PCG iterate from dx_c = 0 is orthogonal to its residual (ba_solver_set_pcg_model_tol
+ * says how far that holds for a long solve).  Device memory O(K + 81 N) (ba_solver_device_bytes), no D x D
  * matrix and none of the dense symbols' limits on N or K; single shard only (shard_world > 1: BA_ERR_ARG).  BA_GET_S: BA_ERR_ARG. */
 typedef enum { BA_QRKIT = 0, BA_QRCHOL = 1, BA_CHOLESKY = 2, BA_MOREQR = 3, BA_QRSPQR = 4, BA_ITERSCHUR = 5 } ba_solver_kind;
 
@@ -286,6 +288,39 @@ typedef struct {
     double last_rel_residual;
 } ba_pcg_stats;
 int ba_solver_pcg_stats(ba_solver *s, ba_pcg_stats *out, int reset);
+/* The model-decrease stopping rule of truncated Newton methods (Nash and Sofer; Ceres' ITERATIVE_SCHUR stops on it by default; DESIGN.md
+ * section 20).
+ * eta = 0: off, a new solver's setting.  0 < eta < 1: a trial's solve ALSO stops at the head of iteration k >= 1 when
+ *   zeta_k = k (s_k - s_{k-1}) / s_k < eta,   s_k = x_k'(rhs + r_k) = -2 Q(x_k),  s_0 = 0,
+ * with Q(x) = x'Sx / 2 - x'rhs the model the reduced system minimises.  The residual rule and the cap of ba_solver_set_pcg stay in
+ * force; whichever holds first ends the solve (residual tested first).  s_k <= 0 or not finite: the rule does not fire.
+ * s_k is summed in fp64 for both scalar types from x_k, rhs and the recurrence's r_k as they are stored (with shared intrinsics all three
+ * are in range(Pi), so the same sum holds).  Takes effect at the next ba_solver_try_step / ba_minimize; drops the captured trial graph like
+ * ba_solver_set_pcg; leaves the linearisation and a pending step alone.  Legal for both scalar types and with every other setting of a
+ * BA_ITERSCHUR solver.  With eta = 0 the solver enqueues the launches and returns the bits of one that never had the rule.
+ * With the rule on, ba_pcg_stats.last_iters is the k at which the solve stopped and last_converged is 1 when either rule stopped it;
+ * last_rel_residual keeps its meaning, the true residual of the returned step -- which is now often well above rel_tol: the rule exists to
+ * stop a solve whose model decrease is complete while its residual is not small.  The LM loop's rhoScale dx'(lambda dx + g) is the
+ * model decrease of such a step up to rounding (x_k is orthogonal to r_k), so the gain ratio is not degraded by it.  The orthogonality is
+ * a property of early iterates: CG loses it geometrically with k in any arithmetic (measured in long double: |x_k'r_k| / s_k <= 7e-18 up
+ * to the rule's stop at eta = 0.01, 1e-4 by k = 81 on problem-21 at lambda = 1e-12 max diag J'J), so a long solve ended by the residual
+ * rule returns a rhoScale that is off by that share.
+ * ba_solver_covariance_pcg does not use the rule (a covariance column is a linear solve, not a Newton step); ba_solver_time_phase(4) uses
+ * the rule in force.
+ * Memory: the first call with eta > 0 allocates one more list of block partials, 3 * ceil(N / 256) * 8 bytes, kept until the solver is
+ * freed and counted by ba_solver_device_bytes.
+ * BA_ERR_ARG, solver unchanged: another kind than BA_ITERSCHUR; eta < 0, eta >= 1 or not finite. */
+int ba_solver_set_pcg_model_tol(ba_solver *s, double eta);
+/* Which rule ended the solves made with eta > 0 (a solve with eta = 0 runs the kernels of a solver without the rule and leaves these
+ * alone), counted like ba_pcg_stats: trials that ba_minimize enqueued behind the row that ended a run are not counted.  A solve that
+ * reaches max_iter with |r| <= rel_tol there counts as ended by the residual.  reset != 0 clears all six after reading them.
+ * BA_ERR_ARG for another kind. */
+typedef struct {
+    long long by_residual, by_model, at_cap; /* solves ended by each, since the last reset */
+    int last_rule;                           /* 0 cap, 1 residual, 2 model */
+    double last_zeta, last_model;            /* zeta_k and s_k at the last solve's final iterate (k >= 1; else 0) */
+} ba_pcg_stop_stats;
+int ba_solver_pcg_stop_stats(ba_solver *s, ba_pcg_stop_stats *out, int reset);
 /* Sum of the handle's device allocations in bytes (every kind; the buffers a sharded solve allocates on its first trial included once
  * they exist). */
 int ba_solver_device_bytes(const ba_solver *s, size_t *bytes);

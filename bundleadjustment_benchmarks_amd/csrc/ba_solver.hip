@@ -63,6 +63,11 @@ template <typename F> void with_flag(bool b, F &&f)
     if (b) f(std::bool_constant<true>{});
     else f(std::bool_constant<false>{});
 }
+template <typename F> void with_flags(bool a, bool b, F &&f)
+{
+    with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { f(A, B); }); });
+}
+template <int V> using int_c = std::integral_constant<int, V>; // (a template argument that is not a flag: k_eval's FUSE)
 
 template <typename T> struct DevBuf {
     T *p = nullptr;
@@ -87,6 +92,8 @@ template <typename T> struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr; n = 0;
     }
+    // a setter stages its new lists in locals and commits them by swapping: the old ones leave with the locals
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
     ~DevBuf() { release(); }
 };
 
@@ -251,8 +258,7 @@ template <typename T> struct Solver final : SolverBase {
         for (auto &sl : ring)
             for (auto &e : sl.e)
                 if (e) (void)hipEventDestroy(e);
-        for (hipGraphExec_t g : {g_trial, g_a, g_b, g_ctl})
-            if (g) (void)hipGraphExecDestroy(g);
+        drop_trial_graphs();
         if (h_lam) (void)hipHostFree(h_lam);
         if (h_log) (void)hipHostFree((void *)h_log);
         if (comm) ba_rccl_destroy(comm);
@@ -574,37 +580,32 @@ template <typename T> struct Solver final : SolverBase {
         fa.rec = d_rec.p; fa.dinv = d_dinv.p; fa.tvec = d_tvec.p; fa.tri = d_tri.p; fa.fresh = &d_lm.p->rec_fresh;
         fa.cmask = d_cmask.p; fa.pfix = d_pfix.p;
         fa.wobs = d_wobs.p; fa.loss = loss_kind; fa.lscale = loss_scale;
-#define BA_EVAL(J, F, ...) hipLaunchKernelGGL((k_eval<T, J, F, ##__VA_ARGS__>), dim3(gE), dim3(256), 0, st, Kl, N, Ml, d_cam[which].p, d_pts[which].p, d_obs_cam.p, d_obs_pt.p, \
-                                         d_meas.p, tau2, d_r.p, d_Jc.p, d_Jp.p, d_JcA.p, d_part_e.p, go, commit ? d_cam[0].p : (T *)nullptr,              \
-                                         commit ? d_pts[0].p : (T *)nullptr, fa)
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
         // eval_coop: the fused CHOLESKY linearisation stores its records a wavefront's run at a time (FUSE = 3 in place of 2) -- except in
         // fp32 on a problem of one round of workgroups, where it measured 2 % slower than the owners' stores (profiles/EXPERIMENTS.md, 7)
         const bool eval_coop = rec_coop && !(sizeof(T) == 4 && gE <= 2 * num_cus);
-        // masked: the same launches through the instantiations that zero the fixed columns (ba_solver_set_constant)
-        // model(): the same launches again through the instantiations of the general measurement model (ba_solver_set_loss /
-        // ba_solver_set_obs_weights); the reference's psi at 0.5 px without weights stays on the kernels it always ran
-        if (model()) {
-            if (!jac) BA_EVAL(false, 0, true, false, true);
-            else if (masked) {
-                if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false, true, true); else BA_EVAL(true, 2, false, true, true); } else BA_EVAL(true, 0, false, true, true); }
-                else if (fused && fuse) BA_EVAL(true, 1, true, true, true);
-                else BA_EVAL(true, 0, true, true, true);
-            }
-            else if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false, false, true); else BA_EVAL(true, 2, false, false, true); } else BA_EVAL(true, 0, false, false, true); }
-            else if (fused && fuse) BA_EVAL(true, 1, true, false, true);
-            else BA_EVAL(true, 0, true, false, true);
+        auto launch = [&](auto JAC, auto FUSE, auto SOA, auto MASK, auto MODEL) {
+            hipLaunchKernelGGL((k_eval<T, JAC(), FUSE(), SOA(), MASK(), MODEL()>), dim3(gE), dim3(256), 0, st, Kl, N, Ml, d_cam[which].p, d_pts[which].p,
+                               d_obs_cam.p, d_obs_pt.p, d_meas.p, tau2, d_r.p, d_Jc.p, d_Jp.p, d_JcA.p, d_part_e.p, go, commit ? d_cam[0].p : (T *)nullptr,
+                               commit ? d_pts[0].p : (T *)nullptr, fa);
+        };
+        // masked: the instantiations that zero the fixed columns (ba_solver_set_constant); the residual-only evaluation has no columns
+        // model(): the instantiations of the general measurement model (ba_solver_set_loss / ba_solver_set_obs_weights); the reference's
+        // psi at 0.5 px without weights stays on the kernels it always ran
+        auto linearisation = [&](auto FUSE, auto SOA) {
+            with_flags(masked, model(), [&](auto MASK, auto MODEL) { launch(std::true_type{}, FUSE, SOA, MASK, MODEL); });
+        };
+        constexpr std::false_type aos{};
+        constexpr std::true_type soa{};
+        // the five (FUSE, SOA) pairs that exist, and no other
+        if (!jac) with_flag(model(), [&](auto MODEL) { launch(std::false_type{}, int_c<0>{}, soa, std::false_type{}, MODEL); });
+        else if (chol_elim()) {
+            if (!(fused && fuse)) linearisation(int_c<0>{}, aos);
+            else if (eval_coop) linearisation(int_c<3>{}, aos);
+            else linearisation(int_c<2>{}, aos);
         }
-        else if (!jac) BA_EVAL(false, 0);
-        else if (masked) {
-            if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false, true); else BA_EVAL(true, 2, false, true); } else BA_EVAL(true, 0, false, true); }
-            else if (fused && fuse) BA_EVAL(true, 1, true, true);
-            else BA_EVAL(true, 0, true, true);
-        }
-        else if (chol_elim()) { if (fused && fuse) { if (eval_coop) BA_EVAL(true, 3, false); else BA_EVAL(true, 2, false); } else BA_EVAL(true, 0, false); }
-        else if (fused && fuse) BA_EVAL(true, 1);
-        else BA_EVAL(true, 0);
-#undef BA_EVAL
+        else if (fused && fuse) linearisation(int_c<1>{}, soa);
+        else linearisation(int_c<0>{}, soa);
     }
 
     // tail: the energy reduction that closes the linearisation, as one more block of the last launch (+ the control segment's end stamp)
@@ -625,6 +626,19 @@ template <typename T> struct Solver final : SolverBase {
         }
         hipLaunchKernelGGL((k_cam_gram_reduce<T>), dim3((N * BA_SLAB + 255) / 256 + (tail ? 1 : 0)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p,
                            d_dslab.p, d_V.p, d_gc.p, go, tail ? *tail : ba_red_job{nullptr, 0, 0, 0}, d_scal.p, tail ? &d_lm.p->t_end : (long long *)nullptr);
+    }
+
+    // The launch sequence of a linearisation at the state `which` (linearize_enqueue; time_phase 1 and 8): r, J and the energy partials,
+    // the gradient and the block diagonals, then what joins them in place.
+    //   priors: behind the linearisation's launches, in front of the trial's k_elim_chol (fused_records());
+    //   relative-pose constraints: records, then the per-camera gather into V / gc.  They touch no point block, so the fused pass's
+    //   elimination records stay valid (fused_records()): V and gc are first read by the assembly / the PCG preparation of the trial.
+    void launch_linearisation(int which, const int *go, bool commit, bool fused, const ba_red_job *tail, bool points)
+    {
+        launch_eval(true, which, go, commit, fused);
+        launch_grad(go, tail, points);
+        if (priors()) launch_prior(true, which, go);
+        if (relposes()) launch_relpose(true, which, go);
     }
 
     // m_functor(x, r); energy; m_functor.df(x, J); JtRes; column norms (BacktrackLevMarqQRChol.h:257-280), host-synchronous
@@ -665,14 +679,8 @@ template <typename T> struct Solver final : SolverBase {
         const bool tail = go != nullptr && !want_dmax && kind != BA_MOREQR && !priors() && !relposes(); // (their energy partials come behind launch_grad)
         // behind a trial the point part of J^T r / J^T J and (CHOLESKY) the elimination of the next trial are part of the k_eval launch;
         // the first, host-synchronous linearisation (lambda0 is not known yet, max diag J^T J is wanted) keeps the separate launches
-        // priors: the prior kernel behind the linearisation's launches, in front of the trial's k_elim_chol (fused_records())
         const bool fz = fuse && go != nullptr && !want_dmax;
-        launch_eval(true, go ? 1 : 0, go, go != nullptr, fz);
-        launch_grad(go, tail ? &jobs.j[0] : nullptr, !fz);
-        if (priors()) launch_prior(true, go ? 1 : 0, go);
-        // relative-pose constraints: records, then the per-camera gather into V / gc.  They touch no point block, so the fused pass's
-        // elimination records stay valid (fused_records()): V and gc are first read by the assembly / the PCG preparation of the trial
-        if (relposes()) launch_relpose(true, go ? 1 : 0, go);
+        launch_linearisation(go ? 1 : 0, go, go != nullptr, fz, tail ? &jobs.j[0] : nullptr, !fz);
         if (kind == BA_MOREQR) { // m_solver.compute(J) + Q^T r, once per outer iteration (BacktrackLevMarqMore.h:288-291): the point blocks ...
             launch_elim_qr(d_scal.p + SC_ZERO, d_rec0.p, d_dinv0.p, d_tvec0.p, d_tri0.p, go, /*thin Q for J2bot*/ more_qr());
             if (more_qr() && (rc = launch_more_outer(go))) return rc; // ... and the dense QR of J2bot(lambda = 0); its part 2 follows where a collective may stand
@@ -695,17 +703,12 @@ template <typename T> struct Solver final : SolverBase {
     void launch_eliminate()
     {
         if (chol_elim()) {
-            if (marq()) // (never the fused linearisation's records: they were made at lambda I)
-                with_flag(rec_coop, [&](auto COOP) {
-                    hipLaunchKernelGGL((k_elim_chol<T, true, COOP()>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
-                                       d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p, (const int *)nullptr, damp_args());
-                });
-            else
-                with_flag(rec_coop, [&](auto COOP) {
-                    hipLaunchKernelGGL((k_elim_chol<T, false, COOP()>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
-                                       d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
-                                       fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr);
-                });
+            // (Marquardt never meets the fused linearisation's records: they were made at lambda I, and fused_records() says so)
+            with_flags(marq(), rec_coop, [&](auto MARQ, auto COOP) {
+                hipLaunchKernelGGL((k_elim_chol<T, MARQ(), COOP()>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
+                                   d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
+                                   fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr, damp_args());
+            });
         } else if (kind == BA_MOREQR) {
             if (Kl > 0) // BacktrackLevMarqMore.h:297-345, the per-trial QR of [R ; sqrt(lambda) I]
                 hipLaunchKernelGGL((k_more_trial<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_scal.p + SC_LAMBDA,
@@ -751,13 +754,12 @@ template <typename T> struct Solver final : SolverBase {
         }
         const int post_blocks = lamf ? (Dp + 2) / 3 : 0;
         const long long nthr = (long long)nred * BA_SLAB;
-        if (nred > 0 && marq())
-            hipLaunchKernelGGL((k_schur_reduce<T, true>), dim3((unsigned)((nthr + 191) / 192) + post_blocks), dim3(192), 0, st, nred, d_red_pairs.p, D, ld,
-                               d_pair_hi.p, d_pair_lo.p, d_pair_chunk_ptr.p, d_slab.p, d_V.p, d_gc.p, d_S.p, lamf, post_blocks, Dp, d_gcg.p, d_dxc.p,
-                               damp_args());
-        else if (nred > 0)
-            hipLaunchKernelGGL((k_schur_reduce<T>), dim3((unsigned)((nthr + 191) / 192) + post_blocks), dim3(192), 0, st, nred, d_red_pairs.p, D, ld,
-                               d_pair_hi.p, d_pair_lo.p, d_pair_chunk_ptr.p, d_slab.p, d_V.p, d_gc.p, d_S.p, lamf, post_blocks, Dp, d_gcg.p, d_dxc.p);
+        if (nred > 0)
+            with_flag(marq(), [&](auto MARQ) {
+                hipLaunchKernelGGL((k_schur_reduce<T, MARQ()>), dim3((unsigned)((nthr + 191) / 192) + post_blocks), dim3(192), 0, st, nred, d_red_pairs.p, D,
+                                   ld, d_pair_hi.p, d_pair_lo.p, d_pair_chunk_ptr.p, d_slab.p, d_V.p, d_gc.p, d_S.p, lamf, post_blocks, Dp, d_gcg.p, d_dxc.p,
+                                   damp_args());
+            });
         // every block of this S is written: the constraints' cross blocks join it here, for a trial and for the covariance alike
         if (relposes())
             hipLaunchKernelGGL((k_relpose_schur<T>), dim3((unsigned)(((size_t)n_rp * 36 + 255) / 256)), dim3(256), 0, st, n_rp, (const int *)d_rp_pair.p,
@@ -955,11 +957,10 @@ template <typename T> struct Solver final : SolverBase {
     void launch_post_reduce()
     {
         if (post_folded()) return;
-        if (marq()) // (single shard: the diagonal of V is the diagonal of J_c'J_c)
-            hipLaunchKernelGGL((k_post_reduce<T, true>), dim3((Dp + 3) / 4), dim3(256), 0, st, D, Dp, ld, d_scal.p + SC_LAMBDA, d_S.p, d_gcg.p, d_dxc.p,
+        with_flag(marq(), [&](auto MARQ) { // (Marquardt is single shard: the diagonal of V is the diagonal of J_c'J_c)
+            hipLaunchKernelGGL((k_post_reduce<T, MARQ()>), dim3((Dp + 3) / 4), dim3(256), 0, st, D, Dp, ld, d_scal.p + SC_LAMBDA, d_S.p, d_gcg.p, d_dxc.p,
                                (const T *)d_V.p, damp_args());
-        else
-        hipLaunchKernelGGL((k_post_reduce<T>), dim3((Dp + 3) / 4), dim3(256), 0, st, D, Dp, ld, d_scal.p + SC_LAMBDA, d_S.p, d_gcg.p, d_dxc.p);
+        });
     }
 
     // ---- BA_ITERSCHUR (ba_pcg.hip.h) ------------------------------------------------------------------------------------------------
@@ -991,10 +992,9 @@ template <typename T> struct Solver final : SolverBase {
         int ntrees = 0, nodes = 0, kept = 0, dropped = 0, largest = 0, width = 6;
         void swap(Forest &o)
         {
-#define BA_SWAP(A) std::swap(A.p, o.A.p); std::swap(A.n, o.A.n)
-            BA_SWAP(tree_ptr); BA_SWAP(node_cam); BA_SWAP(node_par); BA_SWAP(node_rec); BA_SWAP(bad); BA_SWAP(in_tree); BA_SWAP(fac); BA_SWAP(u);
-            BA_SWAP(work); BA_SWAP(part); BA_SWAP(edge_ptr); BA_SWAP(edge_oo); BA_SWAP(xc); BA_SWAP(tpart);
-#undef BA_SWAP
+            tree_ptr.swap(o.tree_ptr); node_cam.swap(o.node_cam); node_par.swap(o.node_par); node_rec.swap(o.node_rec); bad.swap(o.bad);
+            in_tree.swap(o.in_tree); fac.swap(o.fac); u.swap(o.u); work.swap(o.work); part.swap(o.part); edge_ptr.swap(o.edge_ptr);
+            edge_oo.swap(o.edge_oo); xc.swap(o.xc); tpart.swap(o.tpart);
             std::swap(width, o.width);
             std::swap(ntrees, o.ntrees); std::swap(nodes, o.nodes); std::swap(kept, o.kept); std::swap(dropped, o.dropped); std::swap(largest, o.largest);
         }
@@ -1133,8 +1133,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipStreamSynchronize(st));
         fo.swap(nf);
         precond_kind = kind; precond_max_tree = max_tree;
-        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl}) // (captured with the old launch sequence)
-            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        drop_trial_graphs(); // (captured with the old launch sequence)
         return BA_OK;
     }
     int precond_info(long long *out6, int *fallback_trees) override
@@ -1169,8 +1168,7 @@ template <typename T> struct Solver final : SolverBase {
         {
             std::swap(ngroups, o.ngroups); std::swap(ngrouped, o.ngrouped); std::swap(largest, o.largest); std::swap(nchunks, o.nchunks);
             std::swap(nslots, o.nslots); std::swap(nwide, o.nwide);
-            std::swap(desc.p, o.desc.p); std::swap(desc.n, o.desc.n); std::swap(members.p, o.members.p); std::swap(members.n, o.members.n);
-            std::swap(wide.p, o.wide.p); std::swap(wide.n, o.wide.n); std::swap(part.p, o.part.p); std::swap(part.n, o.part.n);
+            desc.swap(o.desc); members.swap(o.members); wide.swap(o.wide); part.swap(o.part);
             h_gptr.swap(o.h_gptr); h_members.swap(o.h_members);
         }
         size_t bytes() const { return bytes_of(desc) + bytes_of(members) + bytes_of(wide) + bytes_of(part); }
@@ -1257,8 +1255,7 @@ template <typename T> struct Solver final : SolverBase {
         }
         HIPCHK(hipStreamSynchronize(st));
         sh.swap(ns);
-        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl}) // (captured with the old launch sequence)
-            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        drop_trial_graphs(); // (captured with the old launch sequence)
         have_step = false; // (xTest is the step of the other group set: its members' f, k1, k2 need not be equal)
         return BA_OK;
     }
@@ -1277,12 +1274,11 @@ template <typename T> struct Solver final : SolverBase {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_prec_chunks<T>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p, d_obs_pt.p,
                                d_rec.p, d_tvec.p, Ml, d_dslab.p);
-        if (marq())
-            hipLaunchKernelGGL((k_pcg_prec_reduce<T, true>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
-                               d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, Bm ? Bm : d_pcg_M.p, rhs ? rhs : d_pcg_b.p, gc_out ? gc_out : d_gcg.p, damp_args());
-        else
-        hipLaunchKernelGGL((k_pcg_prec_reduce<T>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p, d_dslab.p,
-                           d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, Bm ? Bm : d_pcg_M.p, rhs ? rhs : d_pcg_b.p, gc_out ? gc_out : d_gcg.p);
+        with_flag(marq(), [&](auto MARQ) {
+            hipLaunchKernelGGL((k_pcg_prec_reduce<T, MARQ()>), dim3((unsigned)(((size_t)N * BA_SLAB + 255) / 256)), dim3(256), 0, st, N, d_cam_dchunk_ptr.p,
+                               d_dslab.p, d_V.p, d_gc.p, d_scal.p + SC_LAMBDA, Bm ? Bm : d_pcg_M.p, rhs ? rhs : d_pcg_b.p, gc_out ? gc_out : d_gcg.p,
+                               damp_args());
+        });
     }
     void launch_pcg_prep()
     {
@@ -1320,12 +1316,10 @@ template <typename T> struct Solver final : SolverBase {
         if (sx.ndchunks > 0)
             hipLaunchKernelGGL((k_pcg_cam_chunks<T, FINAL>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, d_dchunk_ptr.p, d_cam_obs.p,
                                d_obs_pt.p, d_rec.p, Ml, d_pcg_w.p, d_dslab.p, d_pcg.p);
-        if (marq())
-            hipLaunchKernelGGL((k_pcg_cam<T, FINAL, true>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
+        with_flag(marq(), [&](auto MARQ) {
+            hipLaunchKernelGGL((k_pcg_cam<T, FINAL, MARQ()>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
                                d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gz(), d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p, damp_args());
-        else
-        hipLaunchKernelGGL((k_pcg_cam<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, d_cam_dchunk_ptr.p, d_dslab.p, d_V.p, lam, d_pcg_z.p, d_pcg_p.p,
-                           d_dxc.p, d_pcg_b.p, pcg_part_rz(), pcg_gz(), d_pcg_y.p, FINAL ? pcg_part_res() : pcg_part_py(), d_pcg.p);
+        });
         if (relposes()) // (+ the constraints' cross blocks: y and the block partials, directly behind)
             hipLaunchKernelGGL((k_pcg_relpose<T, FINAL>), dim3(pcg_gq), dim3(256), 0, st, k, N, relpose_csr(), (const T *)d_pcg_z.p, (const T *)d_pcg_p.p,
                                (const T *)d_dxc.p, (const T *)d_pcg_b.p, (const double *)pcg_part_rz(), pcg_gz(), d_pcg_y.p,
@@ -1857,30 +1851,16 @@ template <typename T> struct Solver final : SolverBase {
         if (Ml > 0) { // the camera retraction rides as one more block at the end of the grid
             const ba_cam_retract_args cr{N, d_cam[0].p, d_dxc.p, d_gcg.p, d_cam[1].p, d_scal.p, (int)SC_RHO_C};
             // masked: the first reader of dx_c behind every kind's reduced solve forces the fixed rows (and fixed points) to a zero step
-            if (marq())
-                with_flag(masked, [&](auto MASKED) {
-                    hipLaunchKernelGGL((k_backsub<T, 8, MASKED(), true>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p,
-                                       d_tvec.p, d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB,
-                                       cr, ba_fix_args{d_cmask.p, d_pfix.p}, damp_diag());
-                });
-            else if (masked)
-                hipLaunchKernelGGL((k_backsub<T, 8, true>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
-                                   d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr,
-                                   ba_fix_args{d_cmask.p, d_pfix.p});
-            else
-                hipLaunchKernelGGL((k_backsub<T, 8>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p, d_tvec.p,
-                                   d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr);
-        } else if (marq())
-            with_flag(masked, [&](auto MASKED) {
-                hipLaunchKernelGGL((k_retract_cams<T, MASKED(), true>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
+            with_flags(masked, marq(), [&](auto MASKED, auto MARQ) {
+                hipLaunchKernelGGL((k_backsub<T, 8, MASKED(), MARQ()>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p,
+                                   d_tvec.p, d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr,
+                                   ba_fix_args{d_cmask.p, d_pfix.p}, damp_diag());
+            });
+        } else // (an empty shard keeps the zero partial sums written at creation)
+            with_flags(masked, marq(), [&](auto MASKED, auto MARQ) {
+                hipLaunchKernelGGL((k_retract_cams<T, MASKED(), MARQ()>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
                                    d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)d_cmask.p, damp_diag());
             });
-        else if (masked) // (an empty shard keeps the zero partial sums written at creation)
-            hipLaunchKernelGGL((k_retract_cams<T, true>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
-                               d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)d_cmask.p);
-        else
-            hipLaunchKernelGGL((k_retract_cams<T>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
-                               d_cam[1].p, d_scal.p, (int)SC_RHO_C);
     }
 
     // ---- parameters held constant (ba_solver_set_constant) ---------------------------------------------------------------------------
@@ -1909,7 +1889,7 @@ template <typename T> struct Solver final : SolverBase {
         if (any && all) return BA_ERR_ARG; // nothing left to optimise
         if (share_on() && !share_mask_uniform(sh.h_gptr, sh.h_members, cm)) return BA_ERR_ARG; // (a shared parameter is fixed for all or for none)
         HIPCHK(hipStreamSynchronize(st));
-        cov_valid = false;
+        cov_valid = false; // (here already: ba_solver_covariance_get reads d_cmask, which an allocation that fails below leaves half set)
         if (!any) { d_cmask.release(); d_pfix.release(); }
         else {
             int rc;
@@ -1923,12 +1903,7 @@ template <typename T> struct Solver final : SolverBase {
             HIPCHK(hipMemcpy(d_pfix.p, hp.data(), hp.size(), hipMemcpyHostToDevice));
         }
         masked = any;
-        // the captured iterations hold the other instantiations (and the buffers' addresses): captured again on the next ba_minimize
-        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl})
-            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
-        mask_pending = true;
-        have_step = false;
-        return BA_OK;
+        return model_changed();
     }
 
     // ---- measurement model (ba_solver_set_loss / ba_solver_set_obs_weights) -----------------------------------------------------------
@@ -1939,12 +1914,12 @@ template <typename T> struct Solver final : SolverBase {
     T loss_scale = (T)0.5;
     DevBuf<T> d_wobs; // [Kl] of this shard, the solver's observation order (like d_meas)
     bool model() const { return loss_kind != BA_LOSS_REFERENCE || loss_scale != (T)0.5 || d_wobs.p != nullptr; }
-    // the captured iterations hold the other instantiations and kernel arguments: captured again on the next ba_minimize
+    // the end of every setter that changes what a linearisation computes (mask, model, priors, constraints): the captured iterations
+    // hold the other instantiations, kernel arguments and buffer addresses and are captured again on the next ba_minimize
     int model_changed()
     {
         cov_valid = false;
-        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl})
-            if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+        drop_trial_graphs();
         mask_pending = true;
         have_step = false;
         return BA_OK;
@@ -2000,13 +1975,12 @@ template <typename T> struct Solver final : SolverBase {
     {
         ba_prior_args<T> pa{n_pr[0], n_pr[1], n_pr[2], d_pr_id[0].p, d_pr_id[1].p, d_pr_id[2].p, d_pr_x0[0].p, d_pr_info[0].p,
                             d_pr_x0[1].p, d_pr_info[1].p, d_pr_x0[2].p, d_pr_info[2].p};
-#define BA_PRIOR(L, M) hipLaunchKernelGGL((k_prior<T, L, M>), dim3(gP), dim3(256), 0, st, pa, N, Ml, (const T *)d_cam[which].p, (const T *)d_pts[which].p, \
-                                          d_U0.p, d_gp.p, d_V.p, d_gc.p, d_part_e.p + gE, d_part_pr.p, d_part_pm.p + gM, go,                         \
-                                          (const unsigned short *)d_cmask.p, (const unsigned char *)d_pfix.p)
-        if (!lin) BA_PRIOR(false, false);
-        else if (masked) BA_PRIOR(true, true);
-        else BA_PRIOR(true, false);
-#undef BA_PRIOR
+        // (the mask is a property of the linearisation: the energy at xTest always runs the unmasked instantiation, MASK = LIN && ...)
+        with_flags(lin, masked, [&](auto LIN, auto MASKED) {
+            hipLaunchKernelGGL((k_prior<T, LIN(), LIN() && MASKED()>), dim3(gP), dim3(256), 0, st, pa, N, Ml, (const T *)d_cam[which].p,
+                               (const T *)d_pts[which].p, d_U0.p, d_gp.p, d_V.p, d_gc.p, d_part_e.p + gE, d_part_pr.p, d_part_pm.p + gM, go,
+                               (const unsigned short *)d_cmask.p, (const unsigned char *)d_pfix.p);
+        });
     }
     // type 0 points (info = L, 9 per prior), 1 centres (L), 2 intrinsics (info = w, 3 per prior)
     int set_priors(int type, int n, const int *ids, const double *x0, const double *info) override
@@ -2052,34 +2026,30 @@ template <typename T> struct Solver final : SolverBase {
             HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
             HIPCHK(hipMemset(npm.p, 0, sizeof(T) * npm.n));
             if (npr.p) HIPCHK(hipMemset(npr.p, 0, sizeof(T) * npr.n));
-            std::swap(d_part_e.p, npe.p); std::swap(d_part_e.n, npe.n);
-            std::swap(d_part_pm.p, npm.p); std::swap(d_part_pm.n, npm.n);
-            std::swap(d_part_pr.p, npr.p); std::swap(d_part_pr.n, npr.n);
+            d_part_e.swap(npe); d_part_pm.swap(npm); d_part_pr.swap(npr);
             gP = gp_new;
         }
-        std::swap(d_pr_id[type].p, nid.p); std::swap(d_pr_id[type].n, nid.n);
-        std::swap(d_pr_x0[type].p, nx0.p); std::swap(d_pr_x0[type].n, nx0.n);
-        std::swap(d_pr_info[type].p, ninfo.p); std::swap(d_pr_info[type].n, ninfo.n);
-        if (type == 0) { std::swap(d_pr_lonely.p, nlone.p); std::swap(d_pr_lonely.n, nlone.n); }
+        d_pr_id[type].swap(nid); d_pr_x0[type].swap(nx0); d_pr_info[type].swap(ninfo);
+        if (type == 0) d_pr_lonely.swap(nlone);
         n_pr[type] = n;
         return model_changed(); // (the old buffers leave with the locals)
     }
-    // the three sums of the last linearisation's partials, in index order
-    int prior_energy(double *out3) override
+    // the energies a linearisation kept aside: q rows of g block partials, each summed in index order in T (zeros for g = 0)
+    int kept_energy(const T *part, int q, int g, double *out)
     {
         if (!chol_elim() || sharded() || !have_lin || mask_pending) return BA_ERR_ARG;
-        out3[0] = out3[1] = out3[2] = 0.0;
-        if (!priors()) return BA_OK;
         std::vector<T> h;
         int rc;
-        if ((rc = dl(d_part_pr.p, 3 * (size_t)gP, h))) return rc;
-        for (int q = 0; q < 3; q++) {
+        if (g > 0 && (rc = dl(part, (size_t)q * g, h))) return rc;
+        for (int r = 0; r < q; r++) {
             T a = 0;
-            for (int b = 0; b < gP; b++) a += h[(size_t)q * gP + b];
-            out3[q] = (double)a;
+            for (int b = 0; b < g; b++) a += h[(size_t)r * g + b];
+            out[r] = (double)a;
         }
         return BA_OK;
     }
+    // the three sums of the last linearisation's partials
+    int prior_energy(double *out3) override { return kept_energy(d_part_pr.p, 3, gP, out3); }
 
     // ---- relative-pose constraints (ba_solver_set_relative_poses; ba_relpose.hip.h) -------------------------------
     // The lists, the per-constraint records and the CSR of every camera's incident constraints (built here, list order); the block
@@ -2098,12 +2068,11 @@ template <typename T> struct Solver final : SolverBase {
     void launch_relpose(bool lin, int which, const int *go)
     {
         ba_relpose_args<T> ra{n_rp, d_rp_pair.p, d_rp_R0.p, d_rp_t0.p, d_rp_Lr.p, d_rp_Lt.p};
-#define BA_RELPOSE(L, M) hipLaunchKernelGGL((k_relpose<T, L, M>), dim3(gR), dim3(256), 0, st, ra, N, (const T *)d_cam[which].p, d_rp_rec.p, \
-                                            d_part_e.p + gE + 3 * gP, d_part_rp.p, go, (const unsigned short *)d_cmask.p)
-        if (!lin) { BA_RELPOSE(false, false); return; }
-        if (masked && d_cmask.p) BA_RELPOSE(true, true);
-        else BA_RELPOSE(true, false);
-#undef BA_RELPOSE
+        with_flags(lin, masked && d_cmask.p, [&](auto LIN, auto MASKED) { // (MASK = LIN && ..., as in launch_prior)
+            hipLaunchKernelGGL((k_relpose<T, LIN(), LIN() && MASKED()>), dim3(gR), dim3(256), 0, st, ra, N, (const T *)d_cam[which].p, d_rp_rec.p,
+                               d_part_e.p + gE + 3 * gP, d_part_rp.p, go, (const unsigned short *)d_cmask.p);
+        });
+        if (!lin) return;
         hipLaunchKernelGGL((k_relpose_gather<T>), dim3((unsigned)(((size_t)N * BA_RP_ENT + 255) / 256)), dim3(256), 0, st, N, relpose_csr(), d_V.p, d_gc.p, go);
     }
     int set_relposes(int n, const int *pairs, const double *R0, const double *t0, const double *Lr, const double *Lt) override
@@ -2160,35 +2129,18 @@ template <typename T> struct Solver final : SolverBase {
             if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gP + 2 * (size_t)gr_new)) || (rc = npr.alloc(2 * (size_t)gr_new))) { (void)hipGetLastError(); return rc; }
             HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
             if (npr.p) HIPCHK(hipMemset(npr.p, 0, sizeof(T) * npr.n));
-            std::swap(d_part_e.p, npe.p); std::swap(d_part_e.n, npe.n);
-            std::swap(d_part_rp.p, npr.p); std::swap(d_part_rp.n, npr.n);
+            d_part_e.swap(npe); d_part_rp.swap(npr);
             gR = gr_new;
         }
-#define BA_SWAP(A, B) std::swap(A.p, B.p); std::swap(A.n, B.n)
-        BA_SWAP(d_rp_pair, npair); BA_SWAP(d_rp_ptr, nptr); BA_SWAP(d_rp_inc, ninc); BA_SWAP(d_rp_R0, nR0); BA_SWAP(d_rp_t0, nt0);
-        BA_SWAP(d_rp_Lr, nLr); BA_SWAP(d_rp_Lt, nLt); BA_SWAP(d_rp_rec, nrec);
-#undef BA_SWAP
+        d_rp_pair.swap(npair); d_rp_ptr.swap(nptr); d_rp_inc.swap(ninc); d_rp_R0.swap(nR0); d_rp_t0.swap(nt0);
+        d_rp_Lr.swap(nLr); d_rp_Lt.swap(nLt); d_rp_rec.swap(nrec);
         n_rp = n;
         fo.swap(nf);
         h_rp_pair.swap(new_pairs);
         return model_changed(); // (the old buffers leave with the locals)
     }
-    // {sum |e_r|^2, sum |e_t|^2} of the last linearisation's partials, in index order
-    int relpose_energy(double *out2) override
-    {
-        if (!chol_elim() || sharded() || !have_lin || mask_pending) return BA_ERR_ARG;
-        out2[0] = out2[1] = 0.0;
-        if (!relposes()) return BA_OK;
-        std::vector<T> h;
-        int rc;
-        if ((rc = dl(d_part_rp.p, 2 * (size_t)gR, h))) return rc;
-        for (int q = 0; q < 2; q++) {
-            T a = 0;
-            for (int b = 0; b < gR; b++) a += h[(size_t)q * gR + b];
-            out2[q] = (double)a;
-        }
-        return BA_OK;
-    }
+    // {sum |e_r|^2, sum |e_t|^2} of the last linearisation's partials
+    int relpose_energy(double *out2) override { return kept_energy(d_part_rp.p, 2, gR, out2); }
 
     ba_red_jobs test_energy_jobs() const
     {
@@ -2263,17 +2215,16 @@ template <typename T> struct Solver final : SolverBase {
         if ((rc = mark(EV_T4))) return rc;
         launch_backsub_retract();
         if (d_pr_lonely.n > 0) { // (points with a prior and no observation: none on a usual problem, no launch then)
-            if (marq())
-                with_flag(masked, [&](auto MASKED) {
+            with_flag(masked, [&](auto MASKED) { // (two kernels, not two instantiations of one: the Marquardt one takes the bounds)
+                const unsigned char *pfix = MASKED() ? (const unsigned char *)d_pfix.p : nullptr;
+                if (marq())
                     hipLaunchKernelGGL((k_prior_lonely_marq<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml,
                                        (const T *)d_U0.p, (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p,
-                                       d_part_bs.p, gB, MASKED() ? (const unsigned char *)d_pfix.p : nullptr, damp_args());
-                });
-            else
-            with_flag(masked, [&](auto MASKED) {
-                hipLaunchKernelGGL((k_prior_lonely<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml, (const T *)d_U0.p,
-                                   (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p, d_part_bs.p, gB,
-                                   MASKED() ? (const unsigned char *)d_pfix.p : nullptr);
+                                       d_part_bs.p, gB, pfix, damp_args());
+                else
+                    hipLaunchKernelGGL((k_prior_lonely<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml,
+                                       (const T *)d_U0.p, (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p,
+                                       d_part_bs.p, gB, pfix);
             });
         }
         if ((rc = mark(EV_T5))) return rc;
@@ -2814,7 +2765,7 @@ template <typename T> struct Solver final : SolverBase {
         for (int k = 0; k < reps; k++) {
             switch (phase) {
             case 0: launch_eval(false, 0); break;
-            case 1: launch_eval(true, 0); launch_grad(); if (priors()) launch_prior(true, 0, nullptr); if (relposes()) launch_relpose(true, 0, nullptr); break;
+            case 1: launch_linearisation(0, nullptr, false, false, nullptr, true); break;
             case 2: launch_eliminate(); break;
             case 3: launch_assemble(); break; // (QRKIT: J2bot instead of S)
             case 4:
@@ -2825,10 +2776,7 @@ template <typename T> struct Solver final : SolverBase {
                 break;
             case 5: launch_backsub_retract(); break;
             case 8: // the linearisation as ba_minimize runs it behind an accepted step: fused point part (+ CHOLESKY: the next trial's records)
-                launch_eval(true, 0, nullptr, false, true);
-                launch_grad(nullptr, nullptr, !fuse);
-                if (priors()) launch_prior(true, 0, nullptr);
-                if (relposes()) launch_relpose(true, 0, nullptr);
+                launch_linearisation(0, nullptr, false, /*fused*/ true, nullptr, /*points*/ !fuse);
                 break;
             case 9: launch_forest_edges(); break;
             case 10: // the forest's factor alone: events around it, per rep (it needs B_a, which the trial inverts in place)

@@ -12,12 +12,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ba_internal.h" /* BA_CHUNK, BA_CHUNK_SINGLE, BA_SHARE_CHUNK, BA_SHARE_LOCAL: shared with the host plans */
 #include "ba_mfma.hip.h"
 
 #define BA_REC 32 /* Z (27), dinv of the point (3), pad (2): 256 B = two cache lines in fp64, one in fp32 */
 #define BA_REC_DINV 27
 #define BA_SLAB 96
-#define BA_CHUNK 64 /* entries of one camera pair per chunk = per wavefront of the pair kernel */
 #define BA_EPS_PSI 1e-15 /* src/Optimization/BAFunctor.h:159 */
 
 __device__ __forceinline__ double tsqrt(double x) { return sqrt(x); }
@@ -1173,7 +1173,6 @@ __global__ __launch_bounds__(256) void k_dbg_atv(int rows, int D, const T *__res
 // off-diagonal pairs) writes its block of S directly; pairs with several chunks (diagonal pairs, heavy pairs) leave partial
 // tiles in a slab that k_schur_reduce sums in chunk order.  No atomics; the summation order is fixed by the static entry order,
 // so the result is run-to-run reproducible.
-#define BA_CHUNK_SINGLE (1 << 16) /* flag in chunk_info.y: the only chunk of its pair */
 typedef int ba_v2i __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double ba_bufload(__amdgpu_buffer_rsrc_t r, unsigned off, const double *)
 {

@@ -26,10 +26,7 @@
 #ifndef BA_PCG_SHARE_HIP_H
 #define BA_PCG_SHARE_HIP_H
 
-#include "ba_pcg.hip.h"
-
-#define BA_SHARE_CHUNK 256 /* members per chunk at most (8 per lane) */
-#define BA_SHARE_LOCAL 8   /* chunks of a group that k_pcg_share finishes itself at most: the chunk slots of a workgroup */
+#include "ba_pcg.hip.h" /* (BA_SHARE_CHUNK, BA_SHARE_LOCAL: ba_internal.h, with ba_plan_share_slots) */
 
 // one chunk slot: members[m0 .. m0 + len) of a group of ng cameras whose chunks are the slots c0 .. c0 + nc - 1 (an empty slot: len 0)
 struct ba_share_chunk { int m0, len, c0, nc, ng; };

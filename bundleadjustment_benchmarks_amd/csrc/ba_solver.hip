@@ -25,7 +25,6 @@
 #include <cstring>
 #include <new>
 #include <numeric>
-#include <queue>
 #include <string>
 #include <type_traits>
 
@@ -85,6 +84,15 @@ template <typename T> struct DevBuf {
         int rc = alloc(h.size());
         if (rc) return rc;
         if (!h.empty() && hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return BA_ERR_HIP;
+        return BA_OK;
+    }
+    // a plan's flat ints (ba_internal.h) as the records the kernels read; the caller asserts the ints per record
+    int upload_ints(const std::vector<int> &h)
+    {
+        static_assert(sizeof(T) % sizeof(int) == 0 && std::is_trivially_copyable<T>::value, "not a record of ints");
+        int rc = alloc(h.size() / (sizeof(T) / sizeof(int)));
+        if (rc) return rc;
+        if (!h.empty() && hipMemcpy(p, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return BA_ERR_HIP;
         return BA_OK;
     }
     void release()
@@ -283,15 +291,9 @@ template <typename T> struct Solver final : SolverBase {
         gB = (int)(((size_t)Ml * 8 + 255) / 256);
         if (gB < 1) gB = 1;
         gE = gK;
-        if (sx.kmax <= 256 && Kl > 0) {
-            std::vector<int> eb(1, 0);
-            int fill = 0; // observations in the current range
-            for (int j = 0; j < Ml; j++) {
-                const int k = sx.pt_ptr[j + 1] - sx.pt_ptr[j];
-                if (fill + k > 256) { eb.push_back(sx.pt_ptr[j]); fill = 0; }
-                fill += k;
-            }
-            eb.push_back(Kl);
+        std::vector<int> eb;
+        ba_plan_eval_ranges(sx, eb);
+        if (!eb.empty()) {
             gE = (int)eb.size() - 1;
             if ((rc = d_eb.upload(eb))) return rc;
             fuse = getenv("BA_NO_FUSE") == nullptr;
@@ -333,8 +335,7 @@ template <typename T> struct Solver final : SolverBase {
             if ((unsigned long long)Kl * BA_REC * sizeof(T) > (256ull << 20)) { schur_wgs = 2; schur_window = 1; }
             if (const char *ev = getenv("BA_SCHUR_WGS")) schur_wgs = std::max(1, std::min(8, atoi(ev)));
             if (const char *ev = getenv("BA_SCHUR_BANDS")) schur_bands = atoi(ev);
-            // Chunks dealt to the wavefronts of the persistent pair kernel, longest first, always to the least loaded wavefront
-            // (cost = batches of eight entries + a constant per chunk); a wavefront's list is then walked in chunk order.
+            if (const char *ev = getenv("BA_SCHUR_WINDOW")) schur_window = std::max(0, atoi(ev));
             if (N > 65535) return BA_ERR_ARG; // (hi | lo << 16 in the chunk descriptor; a reduced matrix of that size would not fit anyway)
             if ((unsigned long long)Kl * BA_REC * sizeof(T) >= 0xf0000000ull) return BA_ERR_ARG; // 32-bit record offsets: <= 15 M observations per shard (fp64)
             {
@@ -344,75 +345,14 @@ template <typename T> struct Solver final : SolverBase {
                                                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_schur_pairs<T, false>, 256, 0);
                 if (oe == hipSuccess && nb >= 1) schur_wgs = std::min(schur_wgs, nb);
             }
-            schur_grid = std::max(1, std::min((sx.nchunks + 3) / 4, schur_wgs * num_cus));
-            const int nband = (schur_bands > 1 && schur_grid >= 8 * schur_bands) ? schur_bands : 1;
-            schur_grid = schur_grid / nband * nband;
-            const int W = 4 * schur_grid, Wb = W / nband;
-            std::vector<int> order((size_t)sx.nchunks), owner((size_t)sx.nchunks), wptr((size_t)W + 1, 0);
-            auto cost = [&](int c) { return 2 * ((sx.chunk_ptr[c + 1] - sx.chunk_ptr[c] + 7) / 8) + 1; };
-            // bands: the chunk list (sorted by row camera, column camera) cut into nband ranges of equal cost; the workgroups with
-            // blockIdx % nband == b (one XCD under the observed round-robin placement) own range b.  Wavefront index: see k_schur_pairs.
-            std::vector<int> bptr((size_t)nband + 1, sx.nchunks);
-            {
-                long long tot = 0, acc = 0;
-                for (int c = 0; c < sx.nchunks; c++) tot += cost(c);
-                bptr[0] = 0;
-                for (int c = 0, b = 1; c < sx.nchunks && b < nband; c++) {
-                    acc += cost(c);
-                    while (b < nband && acc >= tot * b / nband) bptr[b++] = c + 1;
-                }
-            }
-            // The dealing goes window by window through the band (schur_window chunks per wavefront and window; 0 = the whole band
-            // is one window): the loads carry over, so the balance is the same, but a wavefront's list now holds a few chunks of
-            // EVERY window, i.e. all wavefronts of the band walk through the (row camera, column camera) order side by side and the
-            // records of one row camera (its observations: ~1 MB at config 5) are in the XCD's L2 when the next column camera's
-            // chunk asks for them.
-            if (const char *ev = getenv("BA_SCHUR_WINDOW")) schur_window = std::max(0, atoi(ev));
-            for (int b = 0; b < nband; b++) {
-                typedef std::pair<long long, int> load_t; // (load, wavefront): min-heap
-                std::priority_queue<load_t, std::vector<load_t>, std::greater<load_t>> heap;
-                for (int w = 0; w < Wb; w++) heap.push(load_t(0, b * Wb + w));
-                const int nb_ = bptr[b + 1] - bptr[b];
-                const long long win = schur_window > 0 ? (long long)schur_window * Wb : (long long)std::max(nb_, 1);
-                for (long long w0 = bptr[b]; w0 < bptr[b + 1]; w0 += win) {
-                    const int w1 = (int)std::min<long long>(w0 + win, bptr[b + 1]);
-                    order.assign(w1 - (int)w0, 0);
-                    std::iota(order.begin(), order.end(), (int)w0);
-                    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
-                    for (int c : order) {
-                        load_t t = heap.top();
-                        heap.pop();
-                        owner[c] = t.second;
-                        wptr[t.second + 1]++;
-                        heap.push(load_t(t.first + cost(c), t.second));
-                    }
-                }
-            }
-            schur_nband = nband;
-            for (int w = 0; w < W; w++) wptr[w + 1] += wptr[w];
-            std::vector<int4> ci((size_t)sx.nchunks);
-            {
-                std::vector<int> cur(wptr.begin(), wptr.end() - 1);
-                for (int c = 0; c < sx.nchunks; c++) { // increasing chunk id inside every wavefront's list
-                    const int q = sx.chunk_pair[c];
-                    // (a diagonal pair always goes through k_schur_reduce, which puts lambda on the diagonal when k_post_reduce is folded away)
-                    const bool single = sx.pair_chunk_ptr[q + 1] - sx.pair_chunk_ptr[q] == 1 && sx.pair_hi[q] != sx.pair_lo[q];
-                    ci[cur[owner[c]]++] = make_int4(sx.chunk_ptr[c], (sx.chunk_ptr[c + 1] - sx.chunk_ptr[c]) | (single ? BA_CHUNK_SINGLE : 0),
-                                                    sx.pair_hi[q] | (sx.pair_lo[q] << 16), c);
-                }
-            }
-            if ((rc = d_wave_ptr.upload(wptr))) return rc;
-            std::vector<int> red;
-            for (int q = 0; q < sx.npairs; q++)
-                if (sx.pair_chunk_ptr[q + 1] - sx.pair_chunk_ptr[q] != 1 || sx.pair_hi[q] == sx.pair_lo[q]) red.push_back(q);
-            nred = (int)red.size();
-            if ((rc = d_red_pairs.upload(red))) return rc;
-            std::vector<int2> en((size_t)sx.E);
-            for (long long e = 0; e < sx.E; e++) { // a self entry carries ~point in place of its column observation (k_schur_pairs)
-                const int r_ = sx.ent_r[(size_t)e], c_ = sx.ent_c[(size_t)e];
-                en[(size_t)e] = make_int2(r_, r_ == c_ ? ~sx.obs_pt[r_] : c_);
-            }
-            if ((rc = d_chunk_info.upload(ci)) || (rc = d_ent.upload(en))) return rc;
+            ba_schur_plan sp; // the chunks dealt to the wavefronts of the persistent pair kernel
+            ba_plan_schur(sx, schur_wgs, num_cus, schur_bands, schur_window, sp);
+            schur_grid = sp.grid; schur_nband = sp.nband;
+            if ((rc = d_wave_ptr.upload(sp.wave_ptr))) return rc;
+            nred = (int)sp.red_pairs.size();
+            if ((rc = d_red_pairs.upload(sp.red_pairs))) return rc;
+            static_assert(sizeof(int4) == 4 * sizeof(int) && sizeof(int2) == 2 * sizeof(int), "ba_schur_plan: 4 ints per chunk, 2 per entry");
+            if ((rc = d_chunk_info.upload_ints(sp.chunk_info)) || (rc = d_ent.upload_ints(sp.ent))) return rc;
         }
         // parameters: bundle_adjustment_large.cpp:81-107 (K00 = -f, R = Rodrigues(omega), distortion (k1 f^2, k2 f^4))
         std::vector<T> cam((size_t)15 * N), pts((size_t)3 * (Ml > 0 ? Ml : 1)), meas((size_t)2 * (Kl > 0 ? Kl : 1));
@@ -785,13 +725,9 @@ template <typename T> struct Solver final : SolverBase {
     int dist_setup()
     {
         if (d_own_off.p) return BA_OK;
-        const int nbc = Dp / NB;
-        std::vector<size_t> fill((size_t)world, 0);
-        std::vector<int> off((size_t)nbc);
-        for (int p = 0; p < nbc; p++) { off[p] = (int)(fill[p % world] / 64); fill[p % world] += (size_t)64 * (size_t)(Dp - 64 * p); }
-        own_chunk = 0;
-        for (size_t f : fill) own_chunk = std::max(own_chunk, f);
-        for (int p = 0; p < nbc; p++) off[p] += (int)((size_t)(p % world) * own_chunk / 64);
+        static_assert(NB == 64, "k_pack_owner counts its offsets in units of 64 scalars");
+        std::vector<int> off;
+        own_chunk = ba_plan_owner_offsets(Dp, NB, world, off);
         int rc;
         if ((rc = d_own_off.upload(off))) return rc;
         if ((rc = d_pack.alloc((size_t)world * own_chunk + (size_t)D + 2))) return rc; // behind the chunks: g_c (D) + the energy
@@ -1039,73 +975,13 @@ template <typename T> struct Solver final : SolverBase {
     // the forest of `pairs` under (kind, max_tree) into `out`; everything that can fail, nothing of the solver touched
     int build_forest(const std::vector<int> &rp_pairs, int kind, int max_tree, Forest &out) const
     {
-        const bool vis = kind == BA_PRECOND_VISIBILITY_FOREST;
-        std::vector<int> pairs(rp_pairs); // L
-        if (vis) {
-            std::vector<int> cp, cw;
-            const int rc = ba_covisibility(N, Ml, sx.pt_ptr.data(), sx.obs_cam.data(), 0, cp, cw);
-            if (rc) return rc;
-            if (pairs.size() / 2 + cp.size() / 2 > (size_t)0x7fffffff) return BA_ERR_NOMEM;
-            pairs.insert(pairs.end(), cp.begin(), cp.end());
-            out.width = 9;
-        }
-        const int n = (int)(pairs.size() / 2);
-        out.dropped = n;
-        out.largest = N > 0 ? 1 : 0;
-        if (kind == BA_PRECOND_BLOCK_JACOBI || n == 0 || max_tree < 2) return BA_OK;
-        std::vector<int> parent((size_t)N), via((size_t)N), order((size_t)N);
-        std::vector<unsigned char> kept((size_t)n);
-        int rc = ba_relpose_forest_plan(N, n, pairs.data(), max_tree, parent.data(), via.data(), order.data(), kept.data());
+        ba_forest_plan fp;
+        int rc = ba_plan_forest(sx, rp_pairs, kind, max_tree, fp);
         if (rc) return rc;
-        for (int q = 0; q < n; q++) out.kept += kept[q];
-        out.dropped = n - out.kept;
-        if (out.kept == 0) return BA_OK;
-        std::vector<unsigned char> in_tree((size_t)N, 0);
-        for (int a = 0; a < N; a++)
-            if (parent[a] >= 0) { in_tree[a] = 1; in_tree[parent[a]] = 1; }
-        std::vector<int> pos((size_t)N, -1), tree_ptr(1, 0), node_cam, node_par, node_rec;
-        for (int k = 0; k < N && in_tree[order[k]]; k++) pos[order[k]] = k; // (the lone cameras are last)
-        for (int k = 0; k < N && in_tree[order[k]]; k++) {
-            const int c = order[k];
-            node_cam.push_back(c);
-            node_par.push_back(parent[c] >= 0 ? pos[parent[c]] : -1);
-            // (a kept co-visibility edge has no constraint on its pair: that one came first in L and would have been kept instead)
-            node_rec.push_back(parent[c] >= 0 && 2 * (size_t)via[c] < rp_pairs.size() ? 2 * via[c] + (pairs[2 * (size_t)via[c]] == c ? 0 : 1) : -1);
-            if (parent[c] < 0) { // the root ends its tree
-                out.largest = std::max(out.largest, k + 1 - tree_ptr.back());
-                tree_ptr.push_back(k + 1);
-            }
-        }
-        out.ntrees = (int)tree_ptr.size() - 1;
-        out.nodes = (int)node_cam.size();
-        if (vis) { // per node the record pairs (o of the node, o' of its parent) of their common points: ascending point, then observation order
-            std::vector<int> cptr((size_t)N + 1, 0), edge_ptr(1, 0), edge_oo;
-            for (int i = 0; i < Kl; i++) cptr[(size_t)sx.obs_cam[i] + 1]++;
-            for (int a = 0; a < N; a++) cptr[a + 1] += cptr[a];
-            const std::vector<int> &co = sx.cam_obs, &op = sx.obs_pt; // (a camera's observations ascend, and with them their points)
-            for (int k = 0; k < out.nodes; k++) {
-                if (node_par[k] >= 0) {
-                    const int a = node_cam[k], b = node_cam[node_par[k]];
-                    int ia = cptr[a], ib = cptr[b];
-                    const int ea = cptr[a + 1], eb = cptr[b + 1];
-                    while (ia < ea && ib < eb) {
-                        const int pa = op[co[ia]], pb = op[co[ib]];
-                        if (pa < pb) ia++;
-                        else if (pb < pa) ib++;
-                        else {
-                            int ra = ia, rb = ib;
-                            while (ra < ea && op[co[ra]] == pa) ra++;
-                            while (rb < eb && op[co[rb]] == pa) rb++;
-                            for (int x = ia; x < ra; x++)
-                                for (int y = ib; y < rb; y++) { edge_oo.push_back(co[x]); edge_oo.push_back(co[y]); }
-                            ia = ra; ib = rb;
-                        }
-                    }
-                    if (edge_oo.size() / 2 > (size_t)0x3fffffff) return BA_ERR_NOMEM;
-                }
-                edge_ptr.push_back((int)(edge_oo.size() / 2));
-            }
-            if ((rc = out.edge_ptr.upload(edge_ptr)) || (rc = out.edge_oo.upload(edge_oo)) || (rc = out.xc.alloc((size_t)out.nodes * 81)) ||
+        out.ntrees = fp.ntrees; out.nodes = fp.nodes; out.kept = fp.kept; out.dropped = fp.dropped; out.largest = fp.largest; out.width = fp.width;
+        if (fp.kept == 0) return BA_OK;
+        if (out.width == 9) {
+            if ((rc = out.edge_ptr.upload(fp.edge_ptr)) || (rc = out.edge_oo.upload(fp.edge_oo)) || (rc = out.xc.alloc((size_t)out.nodes * 81)) ||
                 (rc = out.tpart.alloc((size_t)out.ntrees))) {
                 (void)hipGetLastError();
                 return rc;
@@ -1113,8 +989,8 @@ template <typename T> struct Solver final : SolverBase {
             HIPCHK(hipMemset(out.xc.p, 0, sizeof(double) * out.xc.n));
             HIPCHK(hipMemset(out.tpart.p, 0, sizeof(double) * out.tpart.n));
         }
-        if ((rc = out.tree_ptr.upload(tree_ptr)) || (rc = out.node_cam.upload(node_cam)) || (rc = out.node_par.upload(node_par)) ||
-            (rc = out.node_rec.upload(node_rec)) || (rc = out.in_tree.upload(in_tree)) || (rc = out.bad.alloc((size_t)out.ntrees)) ||
+        if ((rc = out.tree_ptr.upload(fp.tree_ptr)) || (rc = out.node_cam.upload(fp.node_cam)) || (rc = out.node_par.upload(fp.node_par)) ||
+            (rc = out.node_rec.upload(fp.node_rec)) || (rc = out.in_tree.upload(fp.in_tree)) || (rc = out.bad.alloc((size_t)out.ntrees)) ||
             (rc = out.fac.alloc((size_t)out.nodes * BA_FOREST_FAC(out.width))) || (rc = out.work.alloc((size_t)out.nodes * 81)) ||
             (rc = out.u.alloc(out.largest > BA_FOREST_LDS ? (size_t)out.nodes * 9 : 0)) ||
             (rc = out.part.alloc((size_t)3 * (pcg_gc + out.ntrees) + (size_t)3 * pcg_gc + 2 * (size_t)pcg_gq))) { (void)hipGetLastError(); return rc; }
@@ -1230,24 +1106,11 @@ template <typename T> struct Solver final : SolverBase {
                     HIPCHK(hipMemcpy(hm.data(), d_cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
                     if (!share_mask_uniform(gptr, members, hm.data())) return BA_ERR_ARG;
                 }
-                std::vector<ba_share_chunk> desc;
-                std::vector<int> wide;
-                for (int g = 0, c = 0; g < ns.ngroups; g++) {
-                    int nc = 0;
-                    while (c + nc < ns.nchunks && cgrp[c + nc] == g) nc++;
-                    if (nc > 1 && nc <= BA_SHARE_LOCAL)
-                        while (desc.size() % 8 + (size_t)nc > 8) desc.push_back(ba_share_chunk{0, 0, 0, 1, 1}); // (an empty slot)
-                    const int c0 = (int)desc.size(), ng = gptr[g + 1] - gptr[g];
-                    for (int k = 0; k < nc; k++) {
-                        if (nc > BA_SHARE_LOCAL) wide.push_back((int)desc.size());
-                        desc.push_back(ba_share_chunk{cptr[c + k], cptr[c + k + 1] - cptr[c + k], c0, nc, ng});
-                    }
-                    ns.largest = std::max(ns.largest, ng);
-                    c += nc;
-                }
-                ns.nslots = (int)desc.size();
-                ns.nwide = (int)wide.size();
-                if ((rc = ns.desc.upload(desc)) || (rc = ns.members.upload(members)) || (rc = ns.wide.upload(wide)) ||
+                ba_share_plan pl;
+                ba_plan_share_slots(ns.ngroups, ns.nchunks, gptr.data(), cptr.data(), cgrp.data(), pl);
+                ns.largest = pl.largest; ns.nslots = pl.nslots; ns.nwide = pl.nwide;
+                static_assert(sizeof(ba_share_chunk) == 5 * sizeof(int), "ba_share_plan: 5 ints per slot");
+                if ((rc = ns.desc.upload_ints(pl.desc)) || (rc = ns.members.upload(members)) || (rc = ns.wide.upload(pl.wide)) ||
                     (rc = ns.part.alloc((size_t)3 * ns.nslots))) { (void)hipGetLastError(); return rc; }
                 HIPCHK(hipMemset(ns.part.p, 0, sizeof(double) * ns.part.n));
                 ns.h_gptr.swap(gptr); ns.h_members.swap(members);
@@ -2111,11 +1974,8 @@ template <typename T> struct Solver final : SolverBase {
         DevBuf<int> npair, nptr, ninc;
         DevBuf<T> nR0, nt0, nLr, nLt, nrec, npe, npr;
         if (n > 0) {
-            std::vector<int> hp(pairs, pairs + 2 * (size_t)n), ptr((size_t)N + 1, 0), inc(2 * (size_t)n);
-            for (int q = 0; q < 2 * n; q++) ptr[hp[q] + 1]++;
-            for (int a = 0; a < N; a++) ptr[a + 1] += ptr[a];
-            std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-            for (int q = 0; q < n; q++) { inc[fill[hp[2 * q]]++] = 2 * q; inc[fill[hp[2 * q + 1]]++] = 2 * q + 1; }
+            std::vector<int> hp(pairs, pairs + 2 * (size_t)n), ptr, inc;
+            ba_plan_relpose_csr(N, n, pairs, ptr, inc);
             auto conv = [](const double *v, size_t cnt) { std::vector<T> h(cnt); for (size_t q = 0; q < cnt; q++) h[q] = (T)v[q]; return h; };
             if ((rc = npair.upload(hp)) || (rc = nptr.upload(ptr)) || (rc = ninc.upload(inc)) || (rc = nR0.upload(conv(R0, (size_t)9 * n))) ||
                 (rc = nt0.upload(conv(t0, (size_t)3 * n))) || (rc = nLr.upload(conv(Lr, (size_t)9 * n))) || (rc = nLt.upload(conv(Lt, (size_t)9 * n))) ||
@@ -2315,6 +2175,20 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
 
+    // the device's SoA [Q][n] as the ABI's AoS [n][Q], and back
+    static void soa_to_aos(const std::vector<T> &h, size_t n, int Q, double *out)
+    {
+        for (size_t i = 0; i < n; i++)
+            for (int q = 0; q < Q; q++) out[Q * i + q] = h[q * n + i];
+    }
+    static std::vector<T> aos_to_soa(const double *in, size_t n, int Q)
+    {
+        std::vector<T> h(Q * n);
+        for (size_t i = 0; i < n; i++)
+            for (int q = 0; q < Q; q++) h[q * n + i] = (T)in[Q * i + q];
+        return h;
+    }
+
     int get(int what, double *out, size_t n) override
     {
         std::vector<T> h, h2;
@@ -2343,15 +2217,15 @@ template <typename T> struct Solver final : SolverBase {
         case BA_GET_JP: {
             if (n != 6 * (size_t)Kl) return BA_ERR_ARG;
             if ((rc = dl(d_Jp.p, 6 * (size_t)Kl, h))) return rc;
-            for (int i = 0; i < Kl; i++)
-                for (int q = 0; q < 6; q++) out[6 * (size_t)i + q] = h[(size_t)q * Kl + i];
+            soa_to_aos(h, Kl, 6, out);
             return BA_OK;
         }
-        case BA_GET_GRAD: {
+        case BA_GET_GRAD:
+        case BA_GET_DX: { // points, then cameras
+            const bool grad = what == BA_GET_GRAD;
             if (n != 3 * (size_t)Ml + D) return BA_ERR_ARG;
-            if ((rc = dl(d_gp.p, 3 * (size_t)Ml, h)) || (rc = dl(d_gc.p, D, h2))) return rc;
-            for (int j = 0; j < Ml; j++)
-                for (int q = 0; q < 3; q++) out[3 * (size_t)j + q] = h[(size_t)q * Ml + j];
+            if ((rc = dl(grad ? d_gp.p : d_dxp.p, 3 * (size_t)Ml, h)) || (rc = dl(grad ? d_gc.p : d_dxc.p, D, h2))) return rc;
+            soa_to_aos(h, Ml, 3, out);
             for (int c = 0; c < D; c++) out[3 * (size_t)Ml + c] = h2[c];
             return BA_OK;
         }
@@ -2373,14 +2247,6 @@ template <typename T> struct Solver final : SolverBase {
                 for (int c = 0; c < D; c++)
                     for (int rr = c; rr < D; rr++) out[(size_t)c * D + rr] = out[(size_t)rr * D + c] = h[(size_t)c * ld + rr];
             }
-            return BA_OK;
-        }
-        case BA_GET_DX: {
-            if (n != 3 * (size_t)Ml + D) return BA_ERR_ARG;
-            if ((rc = dl(d_dxp.p, 3 * (size_t)Ml, h)) || (rc = dl(d_dxc.p, D, h2))) return rc;
-            for (int j = 0; j < Ml; j++)
-                for (int q = 0; q < 3; q++) out[3 * (size_t)j + q] = h[(size_t)q * Ml + j];
-            for (int c = 0; c < D; c++) out[3 * (size_t)Ml + c] = h2[c];
             return BA_OK;
         }
         case 11: { // diagnostic (QRKIT / QRSPQR, single shard, behind a step): the diagonal of R of the dense QR of J2bot (= the betas of the top TSQR level)
@@ -2436,16 +2302,14 @@ template <typename T> struct Solver final : SolverBase {
         case BA_GET_CAMS_TEST: {
             if (n != 15 * (size_t)N) return BA_ERR_ARG;
             if ((rc = dl(d_cam[what == BA_GET_CAMS ? 0 : 1].p, 15 * (size_t)N, h))) return rc;
-            for (int a = 0; a < N; a++)
-                for (int q = 0; q < 15; q++) out[15 * (size_t)a + q] = h[(size_t)q * N + a];
+            soa_to_aos(h, N, 15, out);
             return BA_OK;
         }
         case BA_GET_POINTS:
         case BA_GET_POINTS_TEST: {
             if (n != 3 * (size_t)Ml) return BA_ERR_ARG;
             if ((rc = dl(d_pts[what == BA_GET_POINTS ? 0 : 1].p, 3 * (size_t)Ml, h))) return rc;
-            for (int j = 0; j < Ml; j++)
-                for (int q = 0; q < 3; q++) out[3 * (size_t)j + q] = h[(size_t)q * Ml + j];
+            soa_to_aos(h, Ml, 3, out);
             return BA_OK;
         }
         }
@@ -2454,18 +2318,14 @@ template <typename T> struct Solver final : SolverBase {
 
     int set_state(const double *cam15, const double *pts) override
     {
-        std::vector<T> h((size_t)(cam15 ? 15 : 0) * N);
-        for (int a = 0; cam15 && a < N; a++)
-            for (int q = 0; q < 15; q++) h[(size_t)q * N + a] = (T)cam15[15 * (size_t)a + q];
+        const std::vector<T> h = cam15 ? aos_to_soa(cam15, N, 15) : std::vector<T>();
         if (cam15 && share_on() && !share_equal(sh.h_gptr, sh.h_members, h.data(), N)) return BA_ERR_ARG; // (state unchanged)
         HIPCHK(hipStreamSynchronize(st));
         cov_valid = false;
         have_lin = false; // (J is another state's)
         if (cam15) HIPCHK(hipMemcpy(d_cam[0].p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
         if (pts && Ml > 0) {
-            std::vector<T> hp((size_t)3 * Ml);
-            for (int j = 0; j < Ml; j++)
-                for (int q = 0; q < 3; q++) hp[(size_t)q * Ml + j] = (T)pts[3 * (size_t)j + q];
+            const std::vector<T> hp = aos_to_soa(pts, Ml, 3);
             HIPCHK(hipMemcpy(d_pts[0].p, hp.data(), sizeof(T) * hp.size(), hipMemcpyHostToDevice));
         }
         have_step = false;

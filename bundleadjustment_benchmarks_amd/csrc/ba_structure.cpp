@@ -1,5 +1,6 @@
 // ba_structure.cpp -- static (iteration-independent) structure of one shard: point-sorted observation order,
-// shard boundaries, camera-pair entry lists and their chunking.  Host code, runs once per solver.
+// shard boundaries, camera-pair entry lists and their chunking, and the plans of the index lists the kernels walk (ba_plan_*: the
+// solver uploads them).  Host code without a HIP call, runs once per solver or setter; tests/plans_check.cpp checks the plans.
 //
 // What it replaces in the reference: the sparsity bookkeeping Eigen does on every call -- setFromTriplets of 24K
 // triplets per outer iteration (src/Optimization/BAFunctor.cpp:95-98), the per-trial row permutation of
@@ -9,8 +10,10 @@
 #include "ba_internal.h"
 
 #include <algorithm>
+#include <functional>
 #include <new>
 #include <numeric>
+#include <queue>
 #include <utility>
 
 int ba_build_structure(const ba_problem *p, int shard_rank, int shard_world, int chunk_len, int dchunk_len, ba_structure *s, bool pairs)
@@ -345,4 +348,222 @@ extern "C" int ba_problem_covisibility(const ba_problem *p, int track_max, long 
         return BA_ERR_NOMEM;
     }
     return BA_OK;
+}
+
+// ---- the plans of the solver's device lists (ba_internal.h) ------------------------------------------------------------------------
+
+void ba_plan_eval_ranges(const ba_structure &s, std::vector<int> &eb)
+{
+    eb.clear();
+    if (s.kmax > 256 || s.Kl <= 0) return;
+    eb.push_back(0);
+    int fill = 0; // observations in the current range
+    for (int j = 0; j < s.Ml; j++) {
+        const int k = s.pt_ptr[j + 1] - s.pt_ptr[j];
+        if (fill + k > 256) { eb.push_back(s.pt_ptr[j]); fill = 0; }
+        fill += k;
+    }
+    eb.push_back(s.Kl);
+}
+
+// Chunks dealt to the wavefronts of the persistent pair kernel, longest first, always to the least loaded wavefront
+// (cost = batches of eight entries + a constant per chunk); a wavefront's list is then walked in chunk order.
+// Every wavefront of the persistent grid must be resident at once (the dealing assumes they run side by side): wgs_per_cu is the
+// occupancy's answer.
+void ba_plan_schur(const ba_structure &sx, int wgs_per_cu, int num_cus, int bands, int window, ba_schur_plan &out)
+{
+    out.grid = std::max(1, std::min((sx.nchunks + 3) / 4, wgs_per_cu * num_cus));
+    const int nband = (bands > 1 && out.grid >= 8 * bands) ? bands : 1;
+    out.grid = out.grid / nband * nband;
+    out.nband = nband;
+    const int W = 4 * out.grid, Wb = W / nband;
+    std::vector<int> order((size_t)sx.nchunks), owner((size_t)sx.nchunks);
+    std::vector<int> &wptr = out.wave_ptr;
+    wptr.assign((size_t)W + 1, 0);
+    auto cost = [&](int c) { return 2 * ((sx.chunk_ptr[c + 1] - sx.chunk_ptr[c] + 7) / 8) + 1; };
+    // bands: the chunk list (sorted by row camera, column camera) cut into nband ranges of equal cost; the workgroups with
+    // blockIdx % nband == b (one XCD under the observed round-robin placement) own range b.  Wavefront index: see k_schur_pairs.
+    std::vector<int> bptr((size_t)nband + 1, sx.nchunks);
+    {
+        long long tot = 0, acc = 0;
+        for (int c = 0; c < sx.nchunks; c++) tot += cost(c);
+        bptr[0] = 0;
+        for (int c = 0, b = 1; c < sx.nchunks && b < nband; c++) {
+            acc += cost(c);
+            while (b < nband && acc >= tot * b / nband) bptr[b++] = c + 1;
+        }
+    }
+    // The dealing goes window by window through the band (`window` chunks per wavefront and window; 0 = the whole band
+    // is one window): the loads carry over, so the balance is the same, but a wavefront's list now holds a few chunks of
+    // EVERY window, i.e. all wavefronts of the band walk through the (row camera, column camera) order side by side and the
+    // records of one row camera (its observations: ~1 MB at config 5) are in the XCD's L2 when the next column camera's
+    // chunk asks for them.
+    for (int b = 0; b < nband; b++) {
+        typedef std::pair<long long, int> load_t; // (load, wavefront): min-heap
+        std::priority_queue<load_t, std::vector<load_t>, std::greater<load_t>> heap;
+        for (int w = 0; w < Wb; w++) heap.push(load_t(0, b * Wb + w));
+        const int nb_ = bptr[b + 1] - bptr[b];
+        const long long win = window > 0 ? (long long)window * Wb : (long long)std::max(nb_, 1);
+        for (long long w0 = bptr[b]; w0 < bptr[b + 1]; w0 += win) {
+            const int w1 = (int)std::min<long long>(w0 + win, bptr[b + 1]);
+            order.assign(w1 - (int)w0, 0);
+            std::iota(order.begin(), order.end(), (int)w0);
+            std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
+            for (int c : order) {
+                load_t t = heap.top();
+                heap.pop();
+                owner[c] = t.second;
+                wptr[t.second + 1]++;
+                heap.push(load_t(t.first + cost(c), t.second));
+            }
+        }
+    }
+    for (int w = 0; w < W; w++) wptr[w + 1] += wptr[w];
+    out.chunk_info.assign(4 * (size_t)sx.nchunks, 0);
+    {
+        std::vector<int> cur(wptr.begin(), wptr.end() - 1);
+        for (int c = 0; c < sx.nchunks; c++) { // increasing chunk id inside every wavefront's list
+            const int q = sx.chunk_pair[c];
+            // (a diagonal pair always goes through k_schur_reduce, which puts lambda on the diagonal when k_post_reduce is folded away)
+            const bool single = sx.pair_chunk_ptr[q + 1] - sx.pair_chunk_ptr[q] == 1 && sx.pair_hi[q] != sx.pair_lo[q];
+            int *ci = &out.chunk_info[4 * (size_t)cur[owner[c]]++];
+            ci[0] = sx.chunk_ptr[c];
+            ci[1] = (sx.chunk_ptr[c + 1] - sx.chunk_ptr[c]) | (single ? BA_CHUNK_SINGLE : 0);
+            ci[2] = sx.pair_hi[q] | (sx.pair_lo[q] << 16);
+            ci[3] = c;
+        }
+    }
+    out.red_pairs.clear();
+    for (int q = 0; q < sx.npairs; q++)
+        if (sx.pair_chunk_ptr[q + 1] - sx.pair_chunk_ptr[q] != 1 || sx.pair_hi[q] == sx.pair_lo[q]) out.red_pairs.push_back(q);
+    out.ent.resize(2 * (size_t)sx.E);
+    for (long long e = 0; e < sx.E; e++) { // a self entry carries ~point in place of its column observation (k_schur_pairs)
+        const int r_ = sx.ent_r[(size_t)e], c_ = sx.ent_c[(size_t)e];
+        out.ent[2 * (size_t)e] = r_;
+        out.ent[2 * (size_t)e + 1] = r_ == c_ ? ~sx.obs_pt[r_] : c_;
+    }
+}
+
+int ba_plan_forest(const ba_structure &sx, const std::vector<int> &rp_pairs, int kind, int max_tree, ba_forest_plan &out)
+{
+    const int N = sx.N;
+    const bool vis = kind == BA_PRECOND_VISIBILITY_FOREST;
+    out = ba_forest_plan();
+    std::vector<int> pairs(rp_pairs); // L
+    if (vis) {
+        std::vector<int> cp, cw;
+        const int rc = ba_covisibility(N, sx.Ml, sx.pt_ptr.data(), sx.obs_cam.data(), 0, cp, cw);
+        if (rc) return rc;
+        if (pairs.size() / 2 + cp.size() / 2 > (size_t)0x7fffffff) return BA_ERR_NOMEM;
+        pairs.insert(pairs.end(), cp.begin(), cp.end());
+        out.width = 9;
+    }
+    const int n = (int)(pairs.size() / 2);
+    out.dropped = n;
+    out.largest = N > 0 ? 1 : 0;
+    if (kind == BA_PRECOND_BLOCK_JACOBI || n == 0 || max_tree < 2) return BA_OK;
+    std::vector<int> parent((size_t)N), via((size_t)N), order((size_t)N);
+    std::vector<unsigned char> kept((size_t)n);
+    const int rc = ba_relpose_forest_plan(N, n, pairs.data(), max_tree, parent.data(), via.data(), order.data(), kept.data());
+    if (rc) return rc;
+    for (int q = 0; q < n; q++) out.kept += kept[q];
+    out.dropped = n - out.kept;
+    if (out.kept == 0) return BA_OK;
+    std::vector<unsigned char> &in_tree = out.in_tree;
+    in_tree.assign((size_t)N, 0);
+    for (int a = 0; a < N; a++)
+        if (parent[a] >= 0) { in_tree[a] = 1; in_tree[parent[a]] = 1; }
+    std::vector<int> pos((size_t)N, -1);
+    std::vector<int> &tree_ptr = out.tree_ptr, &node_cam = out.node_cam, &node_par = out.node_par, &node_rec = out.node_rec;
+    tree_ptr.assign(1, 0);
+    for (int k = 0; k < N && in_tree[order[k]]; k++) pos[order[k]] = k; // (the lone cameras are last)
+    for (int k = 0; k < N && in_tree[order[k]]; k++) {
+        const int c = order[k];
+        node_cam.push_back(c);
+        node_par.push_back(parent[c] >= 0 ? pos[parent[c]] : -1);
+        // (a kept co-visibility edge has no constraint on its pair: that one came first in L and would have been kept instead)
+        node_rec.push_back(parent[c] >= 0 && 2 * (size_t)via[c] < rp_pairs.size() ? 2 * via[c] + (pairs[2 * (size_t)via[c]] == c ? 0 : 1) : -1);
+        if (parent[c] < 0) { // the root ends its tree
+            out.largest = std::max(out.largest, k + 1 - tree_ptr.back());
+            tree_ptr.push_back(k + 1);
+        }
+    }
+    out.ntrees = (int)tree_ptr.size() - 1;
+    out.nodes = (int)node_cam.size();
+    if (vis) { // per node the record pairs (o of the node, o' of its parent) of their common points: ascending point, then observation order
+        std::vector<int> cptr((size_t)N + 1, 0);
+        std::vector<int> &edge_ptr = out.edge_ptr, &edge_oo = out.edge_oo;
+        edge_ptr.assign(1, 0);
+        for (int i = 0; i < sx.Kl; i++) cptr[(size_t)sx.obs_cam[i] + 1]++;
+        for (int a = 0; a < N; a++) cptr[a + 1] += cptr[a];
+        const std::vector<int> &co = sx.cam_obs, &op = sx.obs_pt; // (a camera's observations ascend, and with them their points)
+        for (int k = 0; k < out.nodes; k++) {
+            if (node_par[k] >= 0) {
+                const int a = node_cam[k], b = node_cam[node_par[k]];
+                int ia = cptr[a], ib = cptr[b];
+                const int ea = cptr[a + 1], eb = cptr[b + 1];
+                while (ia < ea && ib < eb) {
+                    const int pa = op[co[ia]], pb = op[co[ib]];
+                    if (pa < pb) ia++;
+                    else if (pb < pa) ib++;
+                    else {
+                        int ra = ia, rb = ib;
+                        while (ra < ea && op[co[ra]] == pa) ra++;
+                        while (rb < eb && op[co[rb]] == pa) rb++;
+                        for (int x = ia; x < ra; x++)
+                            for (int y = ib; y < rb; y++) { edge_oo.push_back(co[x]); edge_oo.push_back(co[y]); }
+                        ia = ra; ib = rb;
+                    }
+                }
+                if (edge_oo.size() / 2 > (size_t)0x3fffffff) return BA_ERR_NOMEM;
+            }
+            edge_ptr.push_back((int)(edge_oo.size() / 2));
+        }
+    }
+    return BA_OK;
+}
+
+// A group of 2 .. BA_SHARE_LOCAL chunks never crosses a workgroup's 8 slots (empty slots in front of it where it would).
+void ba_plan_share_slots(int ngroups, int nchunks, const int *gptr, const int *cptr, const int *cgrp, ba_share_plan &out)
+{
+    out = ba_share_plan();
+    std::vector<int> &desc = out.desc;
+    auto slot = [&](int m0, int len, int c0, int nc, int ng) { desc.insert(desc.end(), {m0, len, c0, nc, ng}); };
+    for (int g = 0, c = 0; g < ngroups; g++) {
+        int nc = 0;
+        while (c + nc < nchunks && cgrp[c + nc] == g) nc++;
+        if (nc > 1 && nc <= BA_SHARE_LOCAL)
+            while (desc.size() / 5 % 8 + (size_t)nc > 8) slot(0, 0, 0, 1, 1); // (an empty slot)
+        const int c0 = (int)(desc.size() / 5), ng = gptr[g + 1] - gptr[g];
+        for (int k = 0; k < nc; k++) {
+            if (nc > BA_SHARE_LOCAL) out.wide.push_back((int)(desc.size() / 5));
+            slot(cptr[c + k], cptr[c + k + 1] - cptr[c + k], c0, nc, ng);
+        }
+        out.largest = std::max(out.largest, ng);
+        c += nc;
+    }
+    out.nslots = (int)(desc.size() / 5);
+    out.nwide = (int)out.wide.size();
+}
+
+void ba_plan_relpose_csr(int N, int n, const int *pairs, std::vector<int> &ptr, std::vector<int> &inc)
+{
+    ptr.assign((size_t)N + 1, 0);
+    inc.resize(2 * (size_t)n);
+    for (int q = 0; q < 2 * n; q++) ptr[pairs[q] + 1]++;
+    for (int a = 0; a < N; a++) ptr[a + 1] += ptr[a];
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int q = 0; q < n; q++) { inc[fill[pairs[2 * q]]++] = 2 * q; inc[fill[pairs[2 * q + 1]]++] = 2 * q + 1; }
+}
+
+size_t ba_plan_owner_offsets(int Dp, int nb, int world, std::vector<int> &off)
+{
+    const int nbc = Dp / nb;
+    std::vector<size_t> fill((size_t)world, 0);
+    off.resize((size_t)nbc);
+    for (int p = 0; p < nbc; p++) { off[p] = (int)(fill[p % world] / nb); fill[p % world] += (size_t)nb * (size_t)(Dp - nb * p); }
+    size_t own_chunk = 0;
+    for (size_t f : fill) own_chunk = std::max(own_chunk, f);
+    for (int p = 0; p < nbc; p++) off[p] += (int)((size_t)(p % world) * own_chunk / nb);
+    return own_chunk;
 }

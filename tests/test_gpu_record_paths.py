@@ -12,6 +12,7 @@ their cooperative loads measured slower and were dropped, profiles/EXPERIMENTS.m
 import numpy as np
 import pytest
 
+import shape_problems as SP
 from test_gpu_parity import _long_track_problem, _ragged_problem
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +153,13 @@ PROBLEMS = {
     "syn131": lambda ba: ba.Problem.synthetic(5, 40, 131, 9),      # one workgroup; a last wavefront with 3 observations
     "syn1200": lambda ba: ba.Problem.synthetic(12, 300, 1200, 78),  # last workgroup: 176 = 2 wavefronts + 48; camera chunks of 100 % 32
     "one": _one_camera_one_point,
+    # tests/shape_problems.py: camera pairs of 1 ... 129 entries; tracks of 1 ... 256 with point-aligned ranges that are exactly full, filled
+    # by one track and split; the same with a track of 257 (no point-aligned ranges: plain ranges of 256, no fused linearisation).  Under
+    # the tests over PROBLEMS: cooperative against per-thread record stores; fused against BA_NO_FUSE=1:
+    # test_designed_shapes_fused_against_the_separate_launches
+    "pairs": lambda ba: SP.get(ba, "pairs")[0],
+    "tracks256": lambda ba: SP.get(ba, "tracks256")[0],
+    "tracks257": lambda ba: SP.get(ba, "tracks257")[0],
 }
 _CACHE = {}
 
@@ -184,6 +192,35 @@ def test_short_lm_runs_on_the_edge_shapes_are_bit_equal(ba, gpu_ok, monkeypatch,
     p = problem(ba, name)
     a, b = both(monkeypatch, lambda: lm_run(ba, p, 2, scalar, 12))
     assert a["rows"] >= 1
+    same(a, b)
+
+
+# ---- the designed shapes: the fused linearisation against the separate launches ------------------------------------------------------
+@pytest.mark.parametrize("kind,trials", [(2, 16), (1, 12)], ids=["CHOLESKY", "QRCHOL"])
+@pytest.mark.parametrize("name", ["pairs", "tracks256", "tracks257"])
+def test_designed_shapes_fused_against_the_separate_launches(ba, gpu_ok, monkeypatch, name, kind, trials):
+    """ba_minimize on the designs of tests/shape_problems.py with the fused linearisation (k_eval<T, true, FUSE>: behind an accepted step it
+    also sums the point part of J'J and J'r and, CHOLESKY, eliminates the points of the trial that follows) and with BA_NO_FUSE=1 (the
+    separate launches: k_point_prep / k_grad_prep, k_elim_chol in front of every trial), cooperative stores in both: the LM table and the
+    final state are the same BITS.  tracks256 is the case this is for -- its first point-aligned ranges are 255 + 1 (exactly full), one
+    256-track (a range of its own) and 127 + 128 | 2 (split); the run must accept steps, or the fused linearisation never ran.  tracks257:
+    a track beyond 256 leaves no point-aligned ranges (ba_plan_eval_ranges; the builder asserts kmax = 257 and the empty plan, and the
+    solver's `fuse` is only ever set when that plan is not empty), so both settings take the separate launches and the comparison only shows
+    that the switch then changes nothing.  fp64: in fp32 the two sequencings part ways by design ("Fused
+    linearisation"), as in tests/test_gpu_parity.py::test_fused_linearisation_is_bit_equal_to_the_separate_launches."""
+    monkeypatch.delenv("BA_REC_PLAIN", raising=False)
+    p, facts = SP.get(ba, name)
+    assert (facts["eval_ranges"] == []) == (name == "tracks257") and (facts["kmax"] > 256) == (name == "tracks257")
+    out = []
+    for nofuse in (False, True):
+        if nofuse:
+            monkeypatch.setenv("BA_NO_FUSE", "1")
+        else:
+            monkeypatch.delenv("BA_NO_FUSE", raising=False)
+        out.append(lm_run(ba, p, kind, 0, trials))
+    monkeypatch.delenv("BA_NO_FUSE", raising=False)
+    a, b = out
+    assert a["rows"] == trials and a["rows"] - a["rejected"] >= 3, (a["rows"], a["rejected"])
     same(a, b)
 
 

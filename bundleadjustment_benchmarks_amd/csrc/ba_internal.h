@@ -92,6 +92,11 @@ struct ba_schur_plan {
 };
 void ba_plan_schur(const ba_structure &s, int wgs_per_cu, int num_cus, int bands, int window, ba_schur_plan &out);
 
+// The grid of k_pairs_gram: the pair workgroups of the plan first (they keep their block indices, and with them their bands), one
+// workgroup per eight chunks of the camera-sorted view behind them.
+struct ba_tail_grid { int pair_wgs, gram_wgs; };
+inline ba_tail_grid ba_plan_tail_grid(int schur_grid, int ndchunks) { return ba_tail_grid{schur_grid, ndchunks > 0 ? (ndchunks + 7) / 8 : 0}; }
+
 // The forest of ba_relpose_forest_plan over L = rp_pairs (BA_PRECOND_VISIBILITY_FOREST: then the co-visibility pairs) in elimination
 // order, tree after tree.  kept == 0: no lists.  BA_ERR_NOMEM when a count leaves 32 bits.
 struct ba_forest_plan {

@@ -612,11 +612,15 @@ __global__ __launch_bounds__(256) void k_point_prep(int Ml, int K, const int *__
 // 54 values are summed over the 32 lanes through LDS (two passes of 27 rows x 32 lanes, each row summed by one lane in
 // lane order -> deterministic).  A lane-per-output mapping walked the 32 observations one after the other and was
 // latency-bound (85 us for 226 k observations).
-template <typename T>
+// PASSES: the 54 rows cross the LDS in that many passes (2: 57 KB in fp64; 3: 38 KB, which leaves four workgroups to a CU -- k_pairs_gram).
+// Every output is one lane's sum over the 32 lanes in lane order whatever the pass it falls into: the same bits.
+template <typename T, int PASSES = 2>
 __device__ __forceinline__ void ba_cam_gram_block(int bid, int ndchunks, int K, const int *__restrict__ dchunk_ptr, const int *__restrict__ cam_obs,
                                                   const T *__restrict__ JcA, T *__restrict__ dslab)
 {
-    __shared__ T xch[8][27][33];
+    static_assert(54 % PASSES == 0, "whole passes");
+    constexpr int ROWS = 54 / PASSES;
+    __shared__ T xch[8][ROWS][33];
     const int gl = threadIdx.x >> 5, g = bid * 8 + gl, sub = threadIdx.x & 31;
     const bool gok = g < ndchunks;
     const int e0 = gok ? dchunk_ptr[g] : 0, len = gok ? dchunk_ptr[g + 1] - e0 : 0;
@@ -638,16 +642,16 @@ __device__ __forceinline__ void ba_cam_gram_block(int bid, int ndchunks, int K, 
         for (int c = 0; c < 9; c++) v[45 + c] = -(a0[c] * r0 + a1[c] * r1);
     }
 #pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
+    for (int pass = 0; pass < PASSES; pass++) {
         __syncthreads();
 #pragma unroll
-        for (int q = 0; q < 27; q++) xch[gl][q][sub] = v[27 * pass + q];
+        for (int q = 0; q < ROWS; q++) xch[gl][q][sub] = v[ROWS * pass + q];
         __syncthreads();
-        if (gok && sub < 27) {
+        if (gok && sub < ROWS) {
             T a = 0;
 #pragma unroll
             for (int l = 0; l < 32; l++) a += xch[gl][sub][l];
-            dslab[(size_t)g * BA_SLAB + 27 * pass + sub] = a;
+            dslab[(size_t)g * BA_SLAB + ROWS * pass + sub] = a;
         }
     }
 }
@@ -1210,104 +1214,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                                                      const T *__restrict__ tvec, int Ml, T *__restrict__ slab, const T *__restrict__ V,
                                                      const T *__restrict__ gc, int D, int ld, T *__restrict__ S)
 {
-    const int lane = threadIdx.x & 63;
-    // wavefront index: the workgroups with equal blockIdx % nband (one XCD, observed) own one band of the chunk list
-    const int wq = ((blockIdx.x % nband) * (gridDim.x / nband) + blockIdx.x / nband) * 4 + (threadIdx.x >> 6);
-    int slot = wave_ptr[wq];
-    const int slot1 = wave_ptr[wq + 1];
-    if (slot >= slot1) return; // (a whole wavefront leaves; the kernel has no workgroup barrier)
-    // the records as a raw buffer: 32-bit byte offsets, immediate offsets in the instruction, 0 for every offset >= rec_bytes
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(rec), 0, (int)rec_bytes, 0x00020000);
-    constexpr unsigned SZ = sizeof(T), RB = BA_REC * SZ, OOB = 0xfffffff0u - 64 * SZ;
-    const int i = lane & 15, k = lane >> 4;
-    const bool la = i < 9;
-    const unsigned lane_off = 3 * i * SZ; // element (i, 0) of Z
-    typedef typename ba_acc<T>::type acc_t;
-    auto entry_of = [&](const int4 ci) { // this lane's entry of the chunk (lanes past the end shadow the last entry, their products are masked)
-        const int n = ci.y & 0xffff;
-        return ent[ci.x + (lane < n ? lane : n - 1)];
-    };
-    int4 ci0 = chunk_info[slot];
-    int4 ci1 = chunk_info[min(slot + 1, slot1 - 1)];
-    int2 en0 = entry_of(ci0);
-    for (; slot < slot1; slot++) {
-        const int2 en1 = entry_of(ci1);                          // next chunk's indices: arrive under this chunk's work
-        const int4 ci2 = chunk_info[min(slot + 2, slot1 - 1)];   // descriptor of the chunk after next
-        const int n = ci0.y & 0xffff;
-        const int hi = ci0.z & 0xffff, lo = (unsigned)ci0.z >> 16, g = ci0.w;
-        const bool diag = hi == lo; // (uniform) only diagonal pairs have self entries, i.e. a reduced-rhs column
-        const int ia_l = en0.x, ib_l = en0.y;
-        acc_t acc;
-#pragma unroll
-        for (int v = 0; v < 4; v++) acc[v] = 0;
-        constexpr int GB = 2; // groups of four entries per batch = what one memory round trip brings in per wavefront (two batches in flight)
-        struct batch_t { T a[3 * GB], d[3 * GB], b[3 * GB]; };
-        auto fetch = [&](int t0, batch_t &o) { // operands of the entries 4 t0 .. 4 (t0 + GB) - 1: lane (i, k) takes entry k of each group
-#pragma unroll
-            for (int u = 0; u < GB; u++) {
-                const int e = 4 * (t0 + u) + k;
-                const bool ok = e < n;
-                const int es = ok ? e : n - 1;
-                const int ia = __shfl(ia_l, es, 64), ibr = __shfl(ib_l, es, 64);
-                const bool self = ibr < 0; // self entry: the column observation is the row observation, ibr = ~point
-                const unsigned ra = (unsigned)ia * RB, rb = (unsigned)(self ? ia : ibr) * RB;
-                const unsigned oa = (ok && la) ? ra + lane_off : OOB, ob = (ok && la) ? rb + lane_off : OOB;
-                const unsigned od = (ok && la) ? ra + BA_REC_DINV * SZ : OOB;
-                ba_bufload3(rsrc, oa, o.a[3 * u], o.a[3 * u + 1], o.a[3 * u + 2]);
-                if (SCALED) ba_bufload3(rsrc, od, o.d[3 * u], o.d[3 * u + 1], o.d[3 * u + 2]);
-                ba_bufload3(rsrc, ob, o.b[3 * u], o.b[3 * u + 1], o.b[3 * u + 2]);
-                if (diag && i == 9 && ok && self) { // column 9 of B: t of the point (reduced rhs)
-#pragma unroll
-                    for (int m = 0; m < 3; m++) o.b[3 * u + m] = tvec[(size_t)m * Ml + (~ibr)];
-                }
-            }
-        };
-        auto multiply = [&](const batch_t &o) {
-#pragma unroll
-            for (int q = 0; q < 3 * GB; q++) acc = ba_mfma(SCALED ? o.a[q] * o.d[q] : o.a[q], o.b[q], acc);
-        };
-        // two register sets, ping-pong (no copies): the next batch is in flight under the MFMAs of the current one
-        const int ngroups = (n + 3) >> 2;
-        batch_t b0, b1;
-        fetch(0, b0);
-        for (int t0 = 0;;) { // (uniform branches)
-            if (t0 + GB < ngroups) fetch(t0 + GB, b1);
-            multiply(b0);
-            t0 += GB;
-            if (t0 >= ngroups) break;
-            if (t0 + GB < ngroups) fetch(t0 + GB, b0);
-            multiply(b1);
-            t0 += GB;
-            if (t0 >= ngroups) break;
-        }
-        // tile element (row r, column j = i): r = ba_crow(k, v)
-        if (ci0.y & BA_CHUNK_SINGLE) {
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const int r = ba_crow<T>(k, v);
-                if (r >= 9) continue;
-                if (i < 9) {
-                    T val = -acc[v];
-                    if (diag) val += V[(size_t)hi * 81 + 9 * r + i];
-                    S[(size_t)(9 * lo + i) * ld + 9 * hi + r] = val;
-                } else if (i == 9 && diag) {
-                    const T gg = gc[9 * hi + r];
-                    S[(size_t)(9 * hi + r) * ld + D] = gg - acc[v];
-                    S[(size_t)(9 * hi + r) * ld + D + 1] = gg;
-                }
-            }
-        } else {
-            T *o = slab + (size_t)g * BA_SLAB;
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const int r = ba_crow<T>(k, v);
-                if (r >= 9) continue;
-                if (i < 9) o[9 * r + i] = acc[v];
-                else if (i == 9) o[81 + r] = acc[v];
-            }
-        }
-        ci0 = ci1; ci1 = ci2; en0 = en1;
+#define BA_PAIRS_BLOCK blockIdx.x
+#define BA_PAIRS_GRID gridDim.x
+#include "ba_schur_pairs_body.hip.h"
+#undef BA_PAIRS_BLOCK
+#undef BA_PAIRS_GRID
+}
+
+// The tail of an LM iteration on the fused-records path (ba_solver.hip, launch_seg_ctl): the persistent pair workgroups of the NEXT trial's
+// assembly at the front of the grid -- they keep their block indices, and with them their XCD bands -- and the camera Gram of the
+// linearisation just made behind them.  The two are independent (the pairs read rec, the Gram reads JcA; production never takes the
+// pairs' `diag` branch, so V and gc are first read by k_schur_reduce) and of opposite kinds: the pairs keep the VALU busy, the Gram waits
+// for its gathers.  asm_go == 0 (the step control has ended the run): the pair workgroups leave; go == 0 (rejected step, J stands): the
+// Gram workgroups leave.  The Gram crosses the LDS in three passes here (38 KB in fp64), so that the launch keeps k_schur_pairs' four
+// workgroups per CU; its registers are the pair part's (profiles/EXPERIMENTS.md section 8).
+template <typename T>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_pairs_gram(int npw, const int *__restrict__ asm_go, const int *__restrict__ wave_ptr, int nband,
+                                                    const int4 *__restrict__ chunk_info, const int2 *__restrict__ ent, const T *__restrict__ rec,
+                                                    unsigned rec_bytes, const T *__restrict__ tvec, int Ml, T *__restrict__ slab, const T *__restrict__ V,
+                                                    const T *__restrict__ gc, int D, int ld, T *__restrict__ S, const int *__restrict__ go, int ndchunks,
+                                                    int K, const int *__restrict__ dchunk_ptr, const int *__restrict__ cam_obs, const T *__restrict__ JcA,
+                                                    T *__restrict__ dslab)
+{
+    if ((int)blockIdx.x >= npw) { // (uniform per workgroup)
+        if (*go != 0) ba_cam_gram_block<T, 3>(blockIdx.x - npw, ndchunks, K, dchunk_ptr, cam_obs, JcA, dslab);
+        return;
     }
+    if (*asm_go == 0) return;
+    constexpr bool SCALED = true; // (CHOLESKY)
+#define BA_PAIRS_BLOCK blockIdx.x
+#define BA_PAIRS_GRID ((unsigned)npw)
+#include "ba_schur_pairs_body.hip.h"
+#undef BA_PAIRS_BLOCK
+#undef BA_PAIRS_GRID
 }
 
 // Sum the chunk partials of each pair with several chunks in chunk order and write the 9x9 block of S (lower block triangle;
@@ -1677,7 +1616,9 @@ template <typename T> struct ba_lm_dev {
     int timed;   // t_ctl / t_end describe the iteration just before this one (not the host-synchronous first linearisation)
     int prev_go; // ... and that iteration linearised
     int prev_code; // decision of the previous trial (accepted + 2 stop): what this shard put into the guard slot of the scalar all-reduce
-    int rec_fresh; // the fused linearisation (k_eval<T, true, FUSE >= 2>) has left the records of the NEXT trial: its k_elim_chol returns at once
+    int rec_fresh; // the fused linearisation (k_eval<T, true, FUSE >= 2>) has left the records of the NEXT trial: its k_elim_chol returns at once    // the iteration's tail that prepares the next trial (ba_solver.hip, launch_seg_ctl): asm_go = the run goes on, the tail assembles;
+    // elim_skip = the tail's k_elim_chol leaves at once (accepted: the fused linearisation makes the records; stopped: nobody wants them)
+    int asm_go, elim_skip;
 };
 // trial_ticks: t_ctl - previous t_end (elimination ... test energy); ctl_ticks_prev: the control segment (control, x = xTest,
 // linearisation) that preceded this trial; both < 0 when unknown
@@ -1793,6 +1734,8 @@ __global__ __launch_bounds__(256 * BA_LM_JOBS) void k_lm_control(T *__restrict__
     scal[sl.lambda] = s.lambda;
     row.stop = failed ? 2.0 : (s.stop ? 1.0 : 0.0);
     s.rec_fresh = 0; // this trial's records are spent; the linearisation behind an accepted step (same control segment) may leave the next ones
+    s.asm_go = s.stop ? 0 : 1;
+    s.elim_skip = (go || s.stop) ? 1 : 0;
     *lm = s;
     host->rows[t % BA_LM_RING] = row;
     host->stop = s.stop;

@@ -187,6 +187,7 @@ template <typename T> struct Solver final : SolverBase {
     int schur_window = 0;
     int nred = 0;
     bool no_fold = false; // BA_NO_FOLD (dev switch): every launch of its own again (A/B timing on one box)
+    bool trial_head = false; // BA_TRIAL_HEAD=1 (dev switch): every trial starts with its own elimination and pair assembly again (A/B, bit-equal)
     bool rec_coop = true; // BA_REC_PLAIN (dev switch) clears it: every thread stores its own record of rec / JcA again (A/B, bit-equal)
     int schur_grid = 1, schur_wgs = 4 /* workgroups of k_schur_pairs per CU */, schur_bands = 8, schur_nband = 1;
     // state: x = d_cam[0], d_pts[0]; xTest = d_cam[1], d_pts[1] (x = xTest is a device-side copy, k_commit)
@@ -232,7 +233,10 @@ template <typename T> struct Solver final : SolverBase {
     // one LM iteration as hipGraphs: world == 1: g_trial = elimination ... test energy, control, x = xTest, linearisation in ONE graph
     // (two graphs with events between them left 18 + 27 us of idle GPU per iteration at config 4: 0.872 -> 0.852 ms);
     // sharded: g_a (elimination, assembly, pack) | all-reduce | g_b (unpack ... test energy) | all-reduce | g_ctl
-    hipGraphExec_t g_trial = nullptr, g_a = nullptr, g_b = nullptr, g_ctl = nullptr;
+    // g_trial_nh: the iteration without its head (elimination, pair assembly) -- the tail of the iteration in front of it has done that
+    // (tail_prepares())
+    hipGraphExec_t g_trial = nullptr, g_trial_nh = nullptr, g_a = nullptr, g_b = nullptr, g_ctl = nullptr;
+    bool seg_head = true; // the segments enqueue_trial is launching or capturing start with the explicit head
     bool use_graph = true;
     hipEvent_t ev[EV_N] = {};
     struct EvSlot { hipEvent_t e[RING_NE]; };
@@ -310,6 +314,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipHostGetDevicePointer((void **)&d_log, (void *)h_log, 0));
         use_graph = getenv("BA_NO_GRAPH") == nullptr;
         no_fold = getenv("BA_NO_FOLD") != nullptr;
+        trial_head = getenv("BA_TRIAL_HEAD") != nullptr && atoi(getenv("BA_TRIAL_HEAD")) != 0;
         rec_coop = getenv("BA_REC_PLAIN") == nullptr;
         dbg_qrcheck = getenv("BA_DBG_QRCHECK") != nullptr;
         dist_factor = getenv("BA_DIST_FACTOR") != nullptr && atoi(getenv("BA_DIST_FACTOR")) != 0;
@@ -549,9 +554,20 @@ template <typename T> struct Solver final : SolverBase {
     }
 
     // tail: the energy reduction that closes the linearisation, as one more block of the last launch (+ the control segment's end stamp)
-    void launch_grad(const int *go = nullptr, const ba_red_job *tail = nullptr, bool points = true /* false: the fused k_eval has done them */)
+    // next_trial (tail_prepares(), behind the step control): the next trial's records on the rejected path and its pair assembly on
+    // both ride here -- the assembly in ONE launch with the camera Gram (k_pairs_gram)
+    void launch_grad(const int *go = nullptr, const ba_red_job *tail = nullptr, bool points = true /* false: the fused k_eval has done them */,
+                     bool next_trial = false)
     {
-        if (!points) {
+        if (next_trial) {
+            if constexpr (sizeof(T) == 8) { // (tail_prepares() says so)
+                launch_eliminate(&d_lm.p->elim_skip); // rejected step: the records at the new lambda (accepted: the fused k_eval has left them)
+                const ba_tail_grid tg = ba_plan_tail_grid(schur_grid, sx.ndchunks);
+                hipLaunchKernelGGL((k_pairs_gram<T>), dim3(tg.pair_wgs + tg.gram_wgs), dim3(256), 0, st, tg.pair_wgs, (const int *)&d_lm.p->asm_go, d_wave_ptr.p,
+                                   schur_nband, d_chunk_info.p, d_ent.p, d_rec.p, (unsigned)(sizeof(T) * d_rec.n), d_tvec.p, Ml, d_slab.p, d_V.p, d_gc.p, D, ld,
+                                   d_S.p, go, sx.ndchunks, Kl, d_dchunk_ptr.p, d_cam_obs.p, d_JcA.p, d_dslab.p);
+            }
+        } else if (!points) {
             if (sx.ndchunks > 0)
                 hipLaunchKernelGGL((k_cam_gram<T>), dim3((sx.ndchunks + 7) / 8), dim3(256), 0, st, sx.ndchunks, Kl,
                                    d_dchunk_ptr.p, d_cam_obs.p, d_JcA.p, d_dslab.p, go);
@@ -573,10 +589,10 @@ template <typename T> struct Solver final : SolverBase {
     //   priors: behind the linearisation's launches, in front of the trial's k_elim_chol (fused_records());
     //   relative-pose constraints: records, then the per-camera gather into V / gc.  They touch no point block, so the fused pass's
     //   elimination records stay valid (fused_records()): V and gc are first read by the assembly / the PCG preparation of the trial.
-    void launch_linearisation(int which, const int *go, bool commit, bool fused, const ba_red_job *tail, bool points)
+    void launch_linearisation(int which, const int *go, bool commit, bool fused, const ba_red_job *tail, bool points, bool next_trial = false)
     {
         launch_eval(true, which, go, commit, fused);
-        launch_grad(go, tail, points);
+        launch_grad(go, tail, points, next_trial);
         if (priors()) launch_prior(true, which, go);
         if (relposes()) launch_relpose(true, which, go);
     }
@@ -607,7 +623,7 @@ template <typename T> struct Solver final : SolverBase {
     // The launches of the linearisation at x.  go != nullptr: conditional on the device-side step control (the kernels return
     // at once unless the trial in front of them was accepted).  The energy lands in SC_ENERGY, or -- sharded -- this shard's part
     // in SC_ELOC.
-    int linearize_enqueue(bool want_dmax, const int *go)
+    int linearize_enqueue(bool want_dmax, const int *go, bool next_trial = false)
     {
         int rc;
         if (!go) HIPCHK(hipEventRecord(ev[EV_L0], st));
@@ -620,7 +636,7 @@ template <typename T> struct Solver final : SolverBase {
         // behind a trial the point part of J^T r / J^T J and (CHOLESKY) the elimination of the next trial are part of the k_eval launch;
         // the first, host-synchronous linearisation (lambda0 is not known yet, max diag J^T J is wanted) keeps the separate launches
         const bool fz = fuse && go != nullptr && !want_dmax;
-        launch_linearisation(go ? 1 : 0, go, go != nullptr, fz, tail ? &jobs.j[0] : nullptr, !fz);
+        launch_linearisation(go ? 1 : 0, go, go != nullptr, fz, tail ? &jobs.j[0] : nullptr, !fz, next_trial);
         if (kind == BA_MOREQR) { // m_solver.compute(J) + Q^T r, once per outer iteration (BacktrackLevMarqMore.h:288-291): the point blocks ...
             launch_elim_qr(d_scal.p + SC_ZERO, d_rec0.p, d_dinv0.p, d_tvec0.p, d_tri0.p, go, /*thin Q for J2bot*/ more_qr());
             if (more_qr() && (rc = launch_more_outer(go))) return rc; // ... and the dense QR of J2bot(lambda = 0); its part 2 follows where a collective may stand
@@ -640,14 +656,15 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
 
-    void launch_eliminate()
+    // skip != nullptr: the launch behind the step control (launch_grad, next_trial); it leaves at once where *skip != 0
+    void launch_eliminate(const int *skip = nullptr)
     {
         if (chol_elim()) {
             // (Marquardt never meets the fused linearisation's records: they were made at lambda I, and fused_records() says so)
             with_flags(marq(), rec_coop, [&](auto MARQ, auto COOP) {
                 hipLaunchKernelGGL((k_elim_chol<T, MARQ(), COOP()>), dim3(gK), dim3(256), 0, st, Kl, Ml, d_obs_pt.p, d_pt_ptr.p, d_JcA.p, d_Jp.p,
                                    d_U0.p, d_gp.p, d_scal.p + SC_LAMBDA, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p,
-                                   fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr, damp_args());
+                                   skip ? skip : fused_records() ? (const int *)&d_lm.p->rec_fresh : (const int *)nullptr, damp_args());
             });
         } else if (kind == BA_MOREQR) {
             if (Kl > 0) // BacktrackLevMarqMore.h:297-345, the per-trial QR of [R ; sqrt(lambda) I]
@@ -680,10 +697,11 @@ template <typename T> struct Solver final : SolverBase {
     bool post_folded() const { return !sharded() && nred > 0 && !no_fold; }
     bool ctl_reduces() const { return !sharded() && !no_fold; }
 
-    void launch_schur()
+    // pairs = false: the tail of the iteration in front of this trial has run them (tail_prepares())
+    void launch_schur(bool pairs = true)
     {
         const T *lamf = post_folded() ? d_scal.p + SC_LAMBDA : nullptr;
-        if (sx.nchunks > 0) {
+        if (pairs && sx.nchunks > 0) {
             // persistent: schur_wgs workgroups per CU, every wavefront walks its own balanced list of chunks (see k_schur_pairs)
             const dim3 gp(schur_grid);
 #define BA_PAIRS(SC) hipLaunchKernelGGL((k_schur_pairs<T, SC>), gp, dim3(256), 0, st, d_wave_ptr.p, schur_nband, d_chunk_info.p, d_ent.p, d_rec.p, \
@@ -1299,7 +1317,7 @@ template <typename T> struct Solver final : SolverBase {
     }
     void drop_trial_graphs()
     {
-        for (hipGraphExec_t *g : {&g_trial, &g_a, &g_b, &g_ctl})
+        for (hipGraphExec_t *g : {&g_trial, &g_trial_nh, &g_a, &g_b, &g_ctl})
             if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
     }
     int pcg_stats(ba_pcg_stats *out, int reset) override
@@ -2038,7 +2056,16 @@ template <typename T> struct Solver final : SolverBase {
     }
 
     // S, or (QRKIT / QRSPQR / MOREQR) the dense J2bot
-    void launch_assemble() { if (dense_qr()) launch_qrkit_build(); else launch_schur(); }
+    void launch_assemble(bool pairs = true) { if (dense_qr()) launch_qrkit_build(); else launch_schur(pairs); }
+    // The tail of an iteration prepares the next trial: behind the step control, which has left the next lambda, the records are made
+    // (the fused k_eval behind an accepted step, k_elim_chol behind a rejected one) and the pairs assembled beside the camera Gram.  The
+    // trial that follows starts at k_schur_reduce (enqueue_trial: head = false).  Where fused_records() holds, for the plain CHOLESKY
+    // solve in fp64 on one shard; every other configuration keeps the head in front of every trial.
+    bool tail_prepares() const
+    {
+        return !trial_head && kind == BA_CHOLESKY && sizeof(T) == 8 && fused_records() && !sharded() && !relposes() && !masked && post_folded() &&
+               sx.nchunks > 0 && sx.ndchunks > 0;
+    }
     // a phase boundary of try_step's timing (ba_timing); nothing in a captured segment
     int mark(int e) { if (step_level) HIPCHK(hipEventRecord(ev[e], st)); return BA_OK; }
     // The segments of one trial (everything behind lambda in SC_LAMBDA).  Single shard: A + B back to back; sharded: the
@@ -2046,10 +2073,11 @@ template <typename T> struct Solver final : SolverBase {
     int launch_seg_a()
     {
         int rc;
-        launch_eliminate();
+        const bool head = seg_head || !tail_prepares();
+        if (head) launch_eliminate();
         if ((rc = mark(EV_T1))) return rc;
         if (iterative()) { launch_pcg_prep(); return mark(EV_T2); } // (single shard: nothing to exchange)
-        launch_assemble();
+        launch_assemble(head);
         if ((rc = mark(EV_T2))) return rc;
         if (dense_qr()) return sharded() ? launch_qr_stack_pack() : BA_OK;
         if (dist_on()) return launch_dist_pack();
@@ -2099,7 +2127,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         ba_lm_slots sl{SC_ENERGY, SC_ETEST, SC_RHO_P, SC_RHO_C, SC_DN_P, SC_DN_C, SC_LAMBDA, SC_ERR, SC_GUARD, world};
         hipLaunchKernelGGL((k_lm_control<T>), dim3(1), dim3(256 * BA_LM_JOBS), 0, st, d_scal.p, d_lm.p, d_log, sl, test_energy_jobs(), ctl_reduces() ? 3 : 0);
-        int rc = linearize_enqueue(false, &d_lm.p->go); // (x = xTest happens inside its first kernel)
+        int rc = linearize_enqueue(false, &d_lm.p->go, tail_prepares()); // (x = xTest happens inside its first kernel)
         if (!rc && more_qr() && !sharded()) rc = more_outer_finish(&d_lm.p->go); // (sharded: behind the segment, it holds an all-reduce -- enqueue_trial)
         return rc;
     }
@@ -2366,7 +2394,9 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
 
-    int enqueue_trial(int slot, bool graphs)
+    // head = false: the trial in front of this one has run in this stream since the last host-side change, and its tail has left this
+    // trial's records and pair blocks (tail_prepares())
+    int enqueue_trial(int slot, bool graphs, bool head)
     {
         int rc;
         EvSlot &e = ring[slot];
@@ -2375,7 +2405,12 @@ template <typename T> struct Solver final : SolverBase {
             spin_next_s = 0;
         }
         if (!sharded()) // ONE graph per LM iteration and no event between the launches: the times come from the device's wall clock
-            return run_seg(&g_trial, &Solver::launch_seg_iter, graphs);
+        {
+            seg_head = head || !tail_prepares();
+            rc = run_seg(seg_head ? &g_trial : &g_trial_nh, &Solver::launch_seg_iter, graphs);
+            seg_head = true; // (try_step and everything else that launches the segments itself)
+            return rc;
+        }
         HIPCHK(hipEventRecord(e.e[0], st));
         {
             if ((rc = run_seg(&g_a, &Solver::launch_seg_a, graphs))) return rc;
@@ -2483,6 +2518,7 @@ template <typename T> struct Solver final : SolverBase {
                 // word instead made that number depend on WHEN a host looked: a rank one trial ahead then sat in ncclAllReduce
                 // for ever.)  Trials behind row s run as no-ops (k_lm_control returns at once, nothing is accepted).
                 auto tprog = std::chrono::steady_clock::now(); // last time the device made progress (a trial finished)
+                bool head = true; // the first trial behind the host's linearisation, or the repeat behind a device error: nobody has prepared it
                 int seen = consumed;
                 while (true) {
                     const int done = drain();
@@ -2494,7 +2530,8 @@ template <typename T> struct Solver final : SolverBase {
                         else if (h_log->rows[need % BA_LM_RING].stop != 0.0) { may = false; final = true; }   // the run ended at row `need`
                     }
                     if (may) {
-                        if ((rc = enqueue_trial(launched % RING_EV, graphs))) break;
+                        if ((rc = enqueue_trial(launched % RING_EV, graphs, head))) break;
+                        head = false;
                         launched++;
                         continue;
                     }
@@ -2540,7 +2577,7 @@ template <typename T> struct Solver final : SolverBase {
                 fprintf(stderr, "ba_mi355x: repeating LM trial %d with the launch-per-step factorisation\n", h.trials - 1);
                 safe_factor = true;
                 recoveries++;
-                for (hipGraphExec_t *g : {&g_trial, &g_b})
+                for (hipGraphExec_t *g : {&g_trial, &g_trial_nh, &g_b})
                     if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
                 h.trials -= 1; h.fun_evals -= 1; // the failed trial's row does not count
                 h.status = BA_RUNNING; h.stop = 0; h.deverr = 0; h.go = 0; h.timed = 0; h.prev_go = 0;
@@ -2594,7 +2631,7 @@ template <typename T> struct Solver final : SolverBase {
                           // ba_minimize meets BA_DEVERR_ROW_FLAG on its first trial and must recover through the launch-per-step path
             if ((D + NB - 1) / NB < 2 || safe_factor) return BA_ERR_ARG; // (a single block column has no fused step)
             fault_rowflag = 1;
-            for (hipGraphExec_t *g : {&g_trial, &g_b})
+            for (hipGraphExec_t *g : {&g_trial, &g_trial_nh, &g_b})
                 if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
             return BA_OK;
         }

@@ -52,6 +52,7 @@ EXPORTS = [
     "ba_intrinsics_group_plan", "ba_solver_set_shared_intrinsics", "ba_solver_shared_intrinsics_info",
     "ba_solver_set_damping", "ba_solver_get_damping",
     "ba_solver_set_pcg_model_tol", "ba_solver_pcg_stop_stats",
+    "ba_dogleg_coefficients", "ba_solver_dogleg_prepare", "ba_solver_try_dogleg", "ba_dogleg_params_default", "ba_minimize_dogleg",
 ]
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
@@ -88,6 +89,23 @@ class PCGStopStats(C.Structure):
 class CovPCGStats(C.Structure):
     _fields_ = [("columns", C.c_longlong), ("batches", C.c_longlong), ("total_iters", C.c_longlong), ("max_iters", C.c_int),
                 ("unconverged", C.c_int), ("worst_rel_residual", C.c_double), ("ms", C.c_double)]
+
+
+class DoglegInfo(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("mu", "g2", "q", "gn2", "g_dot_gn", "alpha", "energy_gn", "rho_scale_gn")]
+
+
+class DoglegParams(C.Structure):
+    """ba_dogleg_params: the radius is in the units of the step (BA_GET_DX); defaults from ba_dogleg_params_default."""
+    _fields_ = [("radius_init", C.c_double), ("radius_min", C.c_double), ("radius_max", C.c_double), ("mu_rel", C.c_double),
+                ("mu_rel_max", C.c_double), ("tol_fun", C.c_double), ("max_iter", C.c_int), ("max_fun_ev", C.c_int),
+                ("max_trials", C.c_int), ("verbose", C.c_int)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        lib().ba_dogleg_params_default(C.byref(p))
+        return p
 
 
 TRIAL_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double)
@@ -154,6 +172,12 @@ def lib():
         L.ba_solver_pcg_stop_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ba_solver_set_damping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         L.ba_solver_get_damping.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_dogleg_coefficients.argtypes = [C.c_double] * 6 + [C.c_void_p] * 4
+        L.ba_solver_dogleg_prepare.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.ba_solver_try_dogleg.argtypes = [C.c_void_p, C.c_double] + [C.c_void_p] * 4
+        L.ba_dogleg_params_default.restype = None
+        L.ba_dogleg_params_default.argtypes = [C.c_void_p]
+        L.ba_minimize_dogleg.argtypes = [C.c_void_p] * 5
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_constant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_problem_gauge_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -365,6 +389,38 @@ class Solver:
         return dict(status=res.status, iterations=res.iterations, trials=res.trials, fun_evals=res.fun_evals,
                     energy=res.energy, lam=res.lambda_, seconds=res.seconds, schur_ms=res.schur_ms,
                     linearize_ms=res.linearize_ms, trace=np.array(rows).reshape(-1, 6))
+
+    # -- Powell's dogleg (CHOLESKY, one shard; include/ba_mi355x.h) ------------------------------------------
+    def dogleg_prepare(self, mu):
+        """The Gauss-Newton step (H + mu I) dx_gn = g of the linearisation in place -- try_step(mu)'s, bit for bit -- kept on the device,
+        and the fp64 scalars of the dogleg: dict(mu, g2, q, gn2, g_dot_gn, alpha, energy_gn, rho_scale_gn)."""
+        info = DoglegInfo()
+        _chk(lib().ba_solver_dogleg_prepare(self._h, float(mu), C.byref(info)), "ba_solver_dogleg_prepare")
+        return {k: getattr(info, k) for k, _ in DoglegInfo._fields_}
+
+    def try_dogleg(self, radius):
+        """The dogleg step of the prepared linearisation for this radius (inf is legal): (e_test, pred, dx_norm, branch), branch 0
+        Gauss-Newton, 1 scaled gradient, 2 interpolated.  get(GET_DX) returns the step; accept() takes it."""
+        e, pr, n, b = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        _chk(lib().ba_solver_try_dogleg(self._h, float(radius), C.byref(e), C.byref(pr), C.byref(n), C.byref(b)), "ba_solver_try_dogleg")
+        return e.value, pr.value, n.value, b.value
+
+    def minimize_dogleg(self, max_trials=0, verbose=False, trace=True, **over):
+        """ba_minimize_dogleg with DoglegParams' defaults and `over` on top: (result dict as minimize()'s without the trace, with
+        `radius` for the final radius; trace [rows, 6]: iter, accepted, f, rho, radius of the trial, elapsed)."""
+        dp = DoglegParams.default()
+        dp.max_trials, dp.verbose = int(max_trials), int(verbose)
+        for k, v in over.items():
+            if not hasattr(dp, k):
+                raise TypeError("DoglegParams has no field %r" % k)
+            setattr(dp, k, v)
+        rows = []
+        cb = TRIAL_CB(lambda user, it, acc, f, rho, rad, el: rows.append((it, acc, f, rho, rad, el))) if trace else None
+        res = Result()
+        _chk(lib().ba_minimize_dogleg(self._h, C.byref(dp), cb, None, C.byref(res)), "ba_minimize_dogleg")
+        out = dict(status=res.status, iterations=res.iterations, trials=res.trials, fun_evals=res.fun_evals, energy=res.energy,
+                   radius=res.lambda_, seconds=res.seconds, schur_ms=res.schur_ms, linearize_ms=res.linearize_ms)
+        return out, np.array(rows).reshape(-1, 6)
 
     def timing(self, reset=False):
         t = Timing()
@@ -660,6 +716,15 @@ def intrinsics_group_plan(N, group_of, chunk=256):
     _chk(lib().ba_intrinsics_group_plan(int(N), _p(group_of), int(chunk), C.byref(ng), _p(group_ptr), _p(members), C.byref(nc), _p(chunk_ptr),
                                         _p(chunk_group)), "ba_intrinsics_group_plan")
     return dict(group_ptr=group_ptr, members=members[:group_ptr[-1]].copy(), chunk_ptr=chunk_ptr, chunk_group=chunk_group)
+
+
+def dogleg_coefficients(g2, q, gn2, g_dot_gn, mu, radius):
+    """ba_dogleg_coefficients (host only): (a, c, branch, pred) of the dogleg step dx = a g + c dx_gn for this radius from the scalars
+    of Solver.dogleg_prepare.  Raises BAError (ERR_ARG) for what the library refuses."""
+    a, c, pr, b = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+    _chk(lib().ba_dogleg_coefficients(float(g2), float(q), float(gn2), float(g_dot_gn), float(mu), float(radius), C.byref(a), C.byref(c),
+                                      C.byref(b), C.byref(pr)), "ba_dogleg_coefficients")
+    return a.value, c.value, b.value, pr.value
 
 
 def relative_pose(cam15, a, b):

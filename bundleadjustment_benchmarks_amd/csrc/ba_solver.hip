@@ -16,6 +16,7 @@
 #include "ba_pcg_share.hip.h"
 #include "ba_prior.hip.h"
 #include "ba_relpose.hip.h"
+#include "ba_dogleg.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -111,6 +112,9 @@ struct SolverBase {
     virtual int linearize(double *energy, double *diag_max) = 0;
     virtual int try_step(double lambda, double *e_test, double *rho_scale, double *dx_norm) = 0;
     virtual int accept() = 0;
+    virtual int dogleg_prepare(double mu, ba_dogleg_info *out) = 0;
+    virtual int try_dogleg(double radius, double *e_test, double *pred, double *dx_norm, int *branch) = 0;
+    virtual int minimize_dogleg(const ba_dogleg_params *dp, ba_trial_cb cb, void *user, ba_result *out) = 0;
     virtual int stats(double *out4) = 0;
     virtual int get(int what, double *out, size_t n) = 0;
     virtual int set_state(const double *cam15, const double *pts) = 0;
@@ -602,6 +606,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         int rc;
         cov_valid = false; // (a covariance is that of the linearisation it was computed from)
+        dl_valid = false;  // (and so is a prepared dogleg)
         if ((rc = linearize_enqueue(diag_max != nullptr, nullptr))) return rc;
         mask_pending = false; // (J, g and the records are now the current mask's)
         if (more_qr() && (rc = more_outer_finish(nullptr))) return rc;
@@ -1350,7 +1355,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg_part_s) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + bytes_of(d_dl_keep) + bytes_of(d_dl_part) + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1800,6 +1805,7 @@ template <typename T> struct Solver final : SolverBase {
     int model_changed()
     {
         cov_valid = false;
+        dl_valid = false;
         drop_trial_graphs();
         mask_pending = true;
         have_step = false;
@@ -2168,12 +2174,193 @@ template <typename T> struct Solver final : SolverBase {
     {
         if (!have_step) return BA_ERR_ARG;
         cov_valid = false;
+        dl_valid = false;
         const int ncam = 15 * N, npts = 3 * Ml;
         hipLaunchKernelGGL((k_commit<T>), dim3((ncam + npts + 255) / 256), dim3(256), 0, st, ncam, npts, d_cam[1].p, d_pts[1].p, d_cam[0].p, d_pts[0].p,
                            (const int *)nullptr);
         HIPCHK(hipStreamSynchronize(st));
         have_step = false;
         return BA_OK;
+    }
+
+    // ---- Powell's dogleg (ba_solver_dogleg_prepare / ba_solver_try_dogleg / ba_minimize_dogleg; ba_dogleg.hip.h) --
+    // State of its own: the copy of dx_gn [3 Ml + D] and one fp64 buffer [q partials: gK | g2, gn2, g'dx_gn partials: 3 dl_gd() |
+    // |dx|^2 partials: gM + 1 | the eight sums], both allocated by the first prepare; the scalars of the last prepare on the host.
+    DevBuf<T> d_dl_keep;
+    DevBuf<double> d_dl_part;
+    bool dl_valid = false; // a prepared dogleg of the linearisation in place: cleared where cov_valid is
+    ba_dogleg_info dli{};
+    enum { DL_Q = 0, DL_G2, DL_GN2, DL_D, DL_DN, DL_NOUT = 8 };
+    int dl_gd() const { return (int)(((size_t)3 * Ml + D + 255) / 256); }
+    double *dl_part_q() const { return d_dl_part.p; }
+    double *dl_part_dots() const { return d_dl_part.p + gK; }
+    double *dl_part_dn() const { return dl_part_dots() + 3 * (size_t)dl_gd(); }
+    double *dl_out() const { return dl_part_dn() + gM + 1; }
+    // what every dogleg call refuses, the solver unchanged
+    bool dogleg_kind_ok() const { return kind == BA_CHOLESKY && !sharded() && !priors() && !relposes() && damp_kind != BA_DAMP_MARQUARDT; }
+    bool dogleg_ok() const { return dogleg_kind_ok() && have_lin && !mask_pending; }
+    int dl_fetch(double *h)
+    {
+        HIPCHK(hipMemcpyAsync(h, dl_out(), sizeof(double) * DL_NOUT, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return BA_OK;
+    }
+
+    void launch_jg()
+    {
+        hipLaunchKernelGGL((k_jg<T>), dim3(gK), dim3(256), 0, st, Kl, Ml, (const int *)d_obs_cam.p, (const int *)d_obs_pt.p, (const T *)d_JcA.p,
+                           (const T *)d_Jp.p, (const T *)d_gc.p, (const T *)d_gp.p, dl_part_q());
+    }
+
+    int dogleg_prepare(double mu, ba_dogleg_info *out) override
+    {
+        if (!dogleg_ok() || !(mu > 0) || !std::isfinite(mu) || !((T)mu > 0) || !std::isfinite((T)mu)) return BA_ERR_ARG;
+        int rc;
+        if (!d_dl_keep.p || !d_dl_part.p) {
+            DevBuf<T> nk;
+            DevBuf<double> np;
+            if ((rc = nk.alloc((size_t)3 * Ml + D)) || (rc = np.alloc((size_t)gK + 3 * (size_t)dl_gd() + gM + 1 + DL_NOUT))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(np.p, 0, sizeof(double) * np.n));
+            d_dl_keep.swap(nk); d_dl_part.swap(np);
+        }
+        dl_valid = false;
+        double e_gn = 0, rs_gn = 0;
+        if ((rc = try_step(mu, &e_gn, &rs_gn, nullptr))) return rc;
+        hipLaunchKernelGGL((k_dogleg_dots<T>), dim3(dl_gd()), dim3(256), 0, st, 3 * Ml, D, (const T *)d_gp.p, (const T *)d_gc.p, (const T *)d_dxp.p,
+                           (const T *)d_dxc.p, d_dl_keep.p, dl_part_dots());
+        launch_jg();
+        ba_red_jobs jobs{};
+        jobs.j[0] = {dl_part_q(), gK, 0, DL_Q};
+        for (int k = 0; k < 3; k++) jobs.j[1 + k] = {dl_part_dots() + (size_t)k * dl_gd(), dl_gd(), 0, DL_G2 + k};
+        hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(4), dim3(256), 0, st, jobs, dl_out(), (const int *)nullptr, (long long *)nullptr);
+        double h[DL_NOUT];
+        if ((rc = dl_fetch(h))) return rc;
+        HIPCHK(hipGetLastError());
+        dli.mu = mu; dli.g2 = h[DL_G2]; dli.q = h[DL_Q]; dli.gn2 = h[DL_GN2]; dli.g_dot_gn = h[DL_D];
+        dli.alpha = dli.g2 > 0 ? dli.g2 / dli.q : 0.0;
+        dli.energy_gn = e_gn; dli.rho_scale_gn = rs_gn;
+        dl_valid = true;
+        if (out) *out = dli;
+        return BA_OK;
+    }
+
+    int try_dogleg(double radius, double *e_test, double *pred, double *dx_norm, int *branch) override
+    {
+        if (!dogleg_ok() || !dl_valid || !(radius > 0)) return BA_ERR_ARG;
+        double a = 0, c = 0, pr = 0;
+        int br = 0, rc;
+        if ((rc = ba_dogleg_coefficients(dli.g2, dli.q, dli.gn2, dli.g_dot_gn, dli.mu, radius, &a, &c, &br, &pr))) return rc;
+        const ba_cam_retract_args cr{N, d_cam[0].p, d_dxc.p, d_gcg.p, d_cam[1].p, d_scal.p, (int)SC_RHO_C};
+        with_flag(masked, [&](auto MASKED) {
+            hipLaunchKernelGGL((k_dogleg_step<T, MASKED()>), dim3(gM + 1), dim3(256), 0, st, Ml, gM, (T)a, (T)c, (const int *)d_pt_ptr.p, (const T *)d_gp.p,
+                               (const T *)d_gc.p, (const T *)d_dl_keep.p, (const T *)d_pts[0].p, d_dxp.p, d_dxc.p, d_pts[1].p,
+                               (const T *)(d_scal.p + SC_LAMBDA), dl_part_dn(), cr, ba_fix_args{d_cmask.p, d_pfix.p});
+        });
+        launch_test_energy();
+        ba_red_jobs jobs{};
+        jobs.j[0] = {dl_part_dn(), gM + 1, 0, DL_DN};
+        hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(1), dim3(256), 0, st, jobs, dl_out(), (const int *)nullptr, (long long *)nullptr);
+        double h[DL_NOUT];
+        if ((rc = fetch_scalars()) || (rc = dl_fetch(h))) return rc;
+        HIPCHK(hipGetLastError());
+        if (e_test) *e_test = (double)h_scal[SC_ETEST];
+        if (pred) *pred = pr;
+        if (dx_norm) *dx_norm = std::sqrt(h[DL_DN]);
+        if (branch) *branch = br;
+        have_step = true;
+        return BA_OK;
+    }
+
+    // The control rule of include/ba_mi355x.h, host-synchronous; tests/dogleg_checks.py holds the same rule in Python.
+    int minimize_dogleg(const ba_dogleg_params *dpp, ba_trial_cb cb, void *user, ba_result *out) override
+    {
+        if (poisoned) return BA_ERR_HIP;
+        ba_dogleg_params dp;
+        if (dpp) dp = *dpp; else ba_dogleg_params_default(&dp);
+        if (!dogleg_kind_ok()) return BA_ERR_ARG; // (the driver linearises itself: a pending mask or model is taken up there)
+        if (!(dp.radius_init >= 0) || !(dp.radius_min > 0) || !(dp.radius_max > 0) || !(dp.mu_rel > 0) || !(dp.mu_rel_max > 0) || !(dp.tol_fun > 0))
+            return BA_ERR_ARG;
+        const auto tbeg = std::chrono::steady_clock::now();
+        const ba_timing tm0 = tm;
+        const bool talk = dp.verbose != 0;
+        if (talk) { // ba_minimize's table; the lambda column holds the radius of the trial
+            printf("############################## Dogleg ##########################################\n");
+            printf("--------------------------------------------------------------------------------\n");
+            printf(" Iter%15s%15s%15s%15s%15s\n", "Status", "f", "rho", "radius", "Elapsed");
+            printf("--------------------------------------------------------------------------------\n");
+        }
+        int rc = BA_OK, status = BA_RUNNING, iter = 0, trials = 0, fun_evals = 0;
+        bool rows_done = false; // max_trials rows have been made
+        double E = 0, dmax = 0, radius = dp.radius_init, m = 1;
+        auto tlast = std::chrono::steady_clock::now();
+        if (dp.max_trials >= 0 && !(rc = linearize(&E, &dmax))) {
+            fun_evals = 1;
+            while (status == BA_RUNNING && !rc && !rows_done) {
+                if (++iter > dp.max_iter) { status = BA_MAX_ITERS; break; }
+                ba_dogleg_info in{};
+                double pred_gn = 0;
+                bool ready = false;
+                while (!ready) { // the Gauss-Newton step of this linearisation; a model that does not decrease: more regularisation, no trial
+                    if (dp.mu_rel * m > dp.mu_rel_max) { status = BA_EXCEEDED_LAMBDA_MAX; break; }
+                    if (fun_evals >= dp.max_fun_ev) { status = BA_TOO_MANY_FUN_EVALS; break; }
+                    if ((rc = dogleg_prepare(dp.mu_rel * m * dmax, &in))) break;
+                    fun_evals++;
+                    if (in.g2 == 0) { status = BA_SUCCESS; break; }
+                    // (scalars the rule refuses -- a step that is not finite: the factorisation broke down -- count as a pred that is not finite)
+                    if (ba_dogleg_coefficients(in.g2, in.q, in.gn2, in.g_dot_gn, in.mu, INFINITY, nullptr, nullptr, nullptr, &pred_gn)) pred_gn = NAN;
+                    if (pred_gn > 0 && std::isfinite(pred_gn)) ready = true;
+                    else m *= 10;
+                }
+                if (!ready) break;
+                m = std::max(1.0, m / 5);
+                const double gn_norm = std::sqrt(in.gn2);
+                if (iter == 1 && radius == 0) radius = gn_norm;
+                for (bool first = true; status == BA_RUNNING && !rc; first = false) {
+                    if (radius < dp.radius_min) { status = BA_EXCEEDED_LAMBDA_MAX; break; }
+                    double e_test = in.energy_gn, pred = pred_gn, dxn = gn_norm;
+                    if (!(first && gn_norm <= radius)) { // (else: the prepare's own xTest, used as it is)
+                        if (fun_evals >= dp.max_fun_ev) { status = BA_TOO_MANY_FUN_EVALS; break; }
+                        if ((rc = try_dogleg(radius, &e_test, &pred, &dxn, nullptr))) break;
+                        fun_evals++;
+                    }
+                    trials++;
+                    rows_done = dp.max_trials > 0 && trials >= dp.max_trials; // (this row is the last: what it decides is still carried out)
+                    const bool accepted = pred > 0 && e_test < E;
+                    const double rho = (E - e_test) / pred;
+                    const auto tnow = std::chrono::steady_clock::now();
+                    const double el = std::chrono::duration<double>(tnow - tlast).count();
+                    tlast = tnow;
+                    if (cb) cb(user, iter, accepted ? 1 : 0, E, rho, radius, el);
+                    if (talk) printf("%5d%15s%15g%15g%15g%14gs\n", iter, accepted ? "Accepted" : "Rejected", E, rho, radius, el);
+                    if (!accepted) {
+                        radius /= 2;
+                        if (rows_done) break;
+                        continue;
+                    }
+                    const bool flat = (E - e_test) / E < dp.tol_fun;
+                    if (rho > 0.75) radius = std::min(dp.radius_max, std::max(radius, 3 * dxn));
+                    else if (rho < 0.25) radius /= 2;
+                    if ((rc = accept())) break;
+                    if (flat) { E = e_test; status = BA_SUCCESS; break; }
+                    rc = linearize(&E, &dmax);
+                    break;
+                }
+            }
+        }
+        if (talk) printf("--------------------------------------------------------------------------------\n");
+        have_step = false;
+        cov_valid = false;
+        dl_valid = false;
+        have_lin = false; // (as behind ba_minimize: a ba_solver_linearize at the final x comes first)
+        if (out) {
+            out->status = status; out->iterations = iter; out->trials = trials; out->fun_evals = fun_evals;
+            out->energy = E; out->lambda = radius;
+            out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tbeg).count();
+            const long long nt = tm.n_trials - tm0.n_trials, nl = tm.n_linearize - tm0.n_linearize;
+            out->schur_ms = nt ? (tm.trial_ms - tm0.trial_ms) / nt : 0.0; // (the prepares: the trials that factor)
+            out->linearize_ms = nl ? (tm.linearize_ms - tm0.linearize_ms) / nl : 0.0;
+        }
+        return rc;
     }
 
     int stats(double *out4) override
@@ -2350,6 +2537,7 @@ template <typename T> struct Solver final : SolverBase {
         if (cam15 && share_on() && !share_equal(sh.h_gptr, sh.h_members, h.data(), N)) return BA_ERR_ARG; // (state unchanged)
         HIPCHK(hipStreamSynchronize(st));
         cov_valid = false;
+        dl_valid = false;
         have_lin = false; // (J is another state's)
         if (cam15) HIPCHK(hipMemcpy(d_cam[0].p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
         if (pts && Ml > 0) {
@@ -2610,6 +2798,7 @@ template <typename T> struct Solver final : SolverBase {
         if (talk) printf("--------------------------------------------------------------------------------\n");
         have_step = false;
         cov_valid = false;
+        dl_valid = false;
         have_lin = false; // (ba_solver_covariance_compute wants a ba_solver_linearize at the final x first)
         if (out) {
             out->status = h.status; out->iterations = h.iter; out->trials = h.trials; out->fun_evals = h.fun_evals;
@@ -2654,6 +2843,7 @@ template <typename T> struct Solver final : SolverBase {
         if (reps < 1 || !ms) return BA_ERR_ARG;
         if (iterative() && (phase == 3 || phase == 6 || phase == 7)) return BA_ERR_ARG; // (no S)
         if ((phase == 9 || phase == 10) && !(iterative() && forest_on() && (phase == 10 || fo.width == 9))) return BA_ERR_ARG;
+        if (phase == 11 && !(dogleg_ok() && d_dl_part.p)) return BA_ERR_ARG; // (k_jg writes the dogleg's partial list: a prepare comes first)
         double acc_ms = 0;
         int rcl = set_lambda((T)lambda_d);
         if (rcl) return rcl;
@@ -2676,6 +2866,7 @@ template <typename T> struct Solver final : SolverBase {
                 launch_linearisation(0, nullptr, false, /*fused*/ true, nullptr, /*points*/ !fuse);
                 break;
             case 9: launch_forest_edges(); break;
+            case 11: launch_jg(); break; // q = |J g|^2 of the dogleg's prepare: the block partials alone (the same values every time)
             case 10: // the forest's factor alone: events around it, per rep (it needs B_a, which the trial inverts in place)
                 launch_pcg_blocks();
                 if (fo.width == 9) launch_forest_edges();
@@ -2830,6 +3021,15 @@ int ba_solver_try_step(ba_solver *s, double lambda, double *energy_test, double 
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->try_step(lambda, energy_test, rho_scale, dx_norm);
 }
 int ba_solver_accept(ba_solver *s) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->accept(); }
+int ba_solver_dogleg_prepare(ba_solver *s, double mu, ba_dogleg_info *out) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->dogleg_prepare(mu, out); }
+int ba_solver_try_dogleg(ba_solver *s, double radius, double *energy_test, double *pred, double *dx_norm, int *branch)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->try_dogleg(radius, energy_test, pred, dx_norm, branch);
+}
+int ba_minimize_dogleg(ba_solver *s, const ba_dogleg_params *p, ba_trial_cb cb, void *user, ba_result *out)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->minimize_dogleg(p, cb, user, out);
+}
 int ba_solver_stats(ba_solver *s, double *out4) { return !(s && out4) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->stats(out4); }
 int ba_solver_get(ba_solver *s, int what, double *out, size_t n) { return !(s && out) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->get(what, out, n); }
 int ba_solver_set_state(ba_solver *s, const double *cam15, const double *pts) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_state(cam15, pts); }

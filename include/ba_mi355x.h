@@ -247,7 +247,8 @@ int ba_solver_timing(ba_solver *s, ba_timing *out, int reset);
  * 6 dense factorisation only, 7 backward sweep only (6 / 7 rebuild S untimed before every repetition).
  * BA_ITERSCHUR: 4 = preconditioner + rhs + the PCG solve; 3, 6 and 7 return BA_ERR_ARG (there is no S); with a forest
  * preconditioner in force 9 = the edge blocks S_ab alone (BA_PRECOND_VISIBILITY_FOREST), 10 = the forest's factor alone (B_a
- * rebuilt untimed before every repetition); BA_ERR_ARG without one. */
+ * rebuilt untimed before every repetition); BA_ERR_ARG without one.  11 = k_jg of ba_solver_dogleg_prepare alone (BA_ERR_ARG unless a
+ * prepare has been made on the linearisation in place; it leaves that prepare valid). */
 int ba_solver_time_phase(ba_solver *s, int phase, int reps, double lambda, double *ms_per_launch);
 
 /* A hand-off between workgroups of one launch that times out (the fused factorisation's row flag, the one-launch back sweep's
@@ -647,6 +648,84 @@ typedef enum { BA_DAMP_IDENTITY = 0, BA_DAMP_MARQUARDT = 1 } ba_damping_kind;
 #define BA_DAMP_DIAG_MAX_DEFAULT 1e32 /* Ceres' max_lm_diagonal */
 int ba_solver_set_damping(ba_solver *s, int kind, double diag_min, double diag_max);
 int ba_solver_get_damping(ba_solver *s, int *kind, double *diag_min, double *diag_max);
+
+/* ---- Powell's dogleg: a second trust-region strategy for BA_CHOLESKY (no reference counterpart; Ceres' DOGLEG, g2o's
+ * OptimizationAlgorithmDogleg, GTSAM's DoglegOptimizer) ---------------------------------------------------------- */
+
+/* All vectors are in the solver's tangent parametrisation, in the order of BA_GET_DX.  With E = sum e^2 the energy, g = -J'e
+ * (BA_GET_GRAD), H = J'J of the last ba_solver_linearize and the model E(x (+) dx) ~ E - 2 g'dx + dx'H dx, the predicted decrease of a
+ * step is pred(dx) = 2 g'dx - dx'H dx (for an LM step: the rhoScale of ba_solver_try_step).  Once per linearisation, for a mu > 0:
+ *   dx_gn solves (H + mu I) dx_gn = g              -- exactly the step of ba_solver_try_step(s, mu)
+ *   dx_sd = alpha g,  alpha = |g|^2 / q,  q = |J g|^2   -- the Cauchy step
+ * and the fp64 scalars g2 = |g|^2, q, gn2 = |dx_gn|^2, g_dot_gn = g'dx_gn are kept.  For a radius > 0 (infinity is legal) the step is
+ * dx = a g + c dx_gn, chosen in this order:
+ *   branch 0 (Gauss-Newton)     sqrt(gn2) <= radius                a = 0, c = 1
+ *   branch 1 (scaled gradient)  else alpha sqrt(g2) >= radius      a = radius / sqrt(g2), c = 0
+ *   branch 2 (interpolated)     else                               a = alpha (1 - beta), c = beta
+ * beta in (0, 1] the root of |dx_sd + beta (dx_gn - dx_sd)| = radius: with A = gn2 - 2 alpha d + alpha^2 g2, B = alpha d - alpha^2 g2,
+ * C = alpha^2 g2 - radius^2 (d = g_dot_gn), beta = (-B + sqrt(B^2 - A C)) / A when B <= 0 and -C / (B + sqrt(B^2 - A C)) otherwise.
+ *   pred = 2 (a g2 + c d) - (a^2 q + 2 a c (g2 - mu d) + c^2 (d - mu gn2))           (H dx_gn = g - mu dx_gn)
+ * g2 = 0: a = c = 0, branch 0, pred = 0.
+ * ba_dogleg_coefficients: this rule, host only (no GPU).  Any output pointer may be NULL.  BA_ERR_ARG: a scalar that is not finite or
+ * is negative, mu <= 0 or not finite, radius <= 0 or NaN, q <= 0 with g2 > 0. */
+typedef struct { double mu, g2, q, gn2, g_dot_gn, alpha, energy_gn, rho_scale_gn; } ba_dogleg_info;
+int ba_dogleg_coefficients(double g2, double q, double gn2, double g_dot_gn, double mu, double radius, double *a, double *c, int *branch,
+                           double *pred);
+/* ba_solver_dogleg_prepare: runs the trial segments of ba_solver_try_step(s, mu) unchanged -- BA_GET_DX, xTest, out->energy_gn and
+ * out->rho_scale_gn are that call's bits, and a ba_solver_accept behind it takes the full Gauss-Newton step -- then keeps a copy of
+ * dx_gn, forms g2, gn2, g_dot_gn (one launch, fused with the copy) and q (k_jg: one pass over J), all accumulated in fp64 for both
+ * scalar types in a fixed order without atomics: the same bits on every run.  alpha = g2 / q (0 when g2 = 0).  `out` may be NULL.
+ * The prepared state survives any number of ba_solver_try_dogleg and ba_solver_try_step calls; ba_solver_linearize, ba_solver_accept,
+ * ba_solver_set_state, ba_minimize, ba_minimize_dogleg, ba_solver_set_constant, ba_solver_set_loss and ba_solver_set_obs_weights
+ * make it stale, as they do a pending step or a computed covariance.
+ * ba_solver_try_dogleg: the coefficients from the kept scalars by ba_dogleg_coefficients on the host, handed to the device as kernel
+ * arguments in the solver's scalar type; one launch forms dx = a g + c dx_gn into the step buffers (BA_GET_DX returns the dogleg step)
+ * and xTest = x (+) dx -- points by addition, cameras by the retraction every trial uses; the test-energy launches of a trial follow.
+ * Returns E(xTest), pred, |dx| (summed in fp64 from the step as stored) and the branch; any pointer may be NULL.  A ba_solver_accept
+ * behind it takes the step.  Branch 0 returns the bits of the prepare: BA_GET_DX, BA_GET_CAMS_TEST, BA_GET_POINTS_TEST and the
+ * test energy (1 * x is x, -0 included; a point nobody observes keeps a zero step and a copy of x).
+ * BA_CHOLESKY, BA_F64 and BA_F32, shard_world == 1; any loss and weights (they are in J); with ba_solver_set_constant a fixed
+ * parameter has g = 0 and dx_gn = 0: its step is exactly 0 and its value keeps its bits, R of an omega-fixed camera included.
+ * BA_ERR_ARG, the solver unchanged: another solver kind; a sharded solver; priors or relative poses set (their rows would have to
+ * enter q: not built); BA_DAMP_MARQUARDT in force (H dx_gn = g - mu D dx_gn and a scaled norm: not built); no valid linearisation, or a
+ * mask or measurement model pending; mu <= 0 or not finite (in the solver's scalar type); radius <= 0 or NaN; ba_solver_try_dogleg
+ * without a valid prepare.
+ * Memory: the first prepare allocates the copy of dx_gn and the lists of block partials, kept until ba_solver_free and counted by
+ * ba_solver_device_bytes:   sizeof(scalar) (3 M + 9 N) + 8 (ceil(K / 256) + 3 ceil((3 M + 9 N) / 256) + ceil(M / 256) + 1 + 8) bytes.
+ * BA_ERR_NOMEM when they do not fit; the solver stays usable. */
+int ba_solver_dogleg_prepare(ba_solver *s, double mu, ba_dogleg_info *out);
+int ba_solver_try_dogleg(ba_solver *s, double radius, double *energy_test, double *pred, double *dx_norm, int *branch);
+
+/* ba_minimize_dogleg: a host-synchronous driver built from ba_solver_linearize, ba_solver_dogleg_prepare, ba_solver_try_dogleg and
+ * ba_solver_accept, one scalar read-back per trial (ba_minimize and its captured graphs are untouched; a device-side control is not
+ * built).  Per outer iteration: mu = mu_rel m max diag(J'J) of this linearisation; m starts at 1 and is multiplied by 10 whenever a
+ * prepare returns a pred of the full Gauss-Newton step that is <= 0 or not finite (scalars that ba_dogleg_coefficients refuses, a step
+ * that is not finite, count as that; such a retry is no trial), the driver gives up
+ * with BA_EXCEEDED_LAMBDA_MAX once mu_rel m > mu_rel_max, and after a good prepare m <- max(1, m / 5).  The first radius is
+ * radius_init, or |dx_gn| of the first iteration when that is 0.  The first trial of an iteration with sqrt(gn2) <= radius is the
+ * prepare's own xTest, used as it is and not evaluated again.  A trial is accepted iff pred > 0 and E_test < E; with
+ * rho = (E - E_test) / pred the radius becomes min(radius_max, max(radius, 3 |dx|)) behind an accepted step with rho > 0.75, radius / 2
+ * behind an accepted step with rho < 0.25 and behind a rejected one.
+ * Status: BA_SUCCESS behind an accepted step with (E - E_test) / E < tol_fun (the step is taken) or when g2 = 0;
+ * BA_EXCEEDED_LAMBDA_MAX when the radius falls below radius_min (or mu_rel m exceeds mu_rel_max); BA_MAX_ITERS; BA_TOO_MANY_FUN_EVALS
+ * (counted: the first linearisation, every prepare, every ba_solver_try_dogleg); BA_RUNNING when max_trials rows have been made.
+ * The callback and the verbose table are ba_minimize's, WITH THE RADIUS OF THE TRIAL IN THE LAMBDA COLUMN; ba_result.lambda is the
+ * final radius.  Refusals: those of ba_solver_dogleg_prepare, decided before anything is touched, and radius_init < 0 or NaN,
+ * radius_min / radius_max / mu_rel / mu_rel_max / tol_fun not positive. */
+typedef struct {
+    double radius_init; /* 0: |dx_gn| of the first iteration */
+    double radius_min;  /* 1e-32 */
+    double radius_max;  /* 1e16  */
+    double mu_rel;      /* 1e-12 (the project's lambda0 rule) */
+    double mu_rel_max;  /* 1     */
+    double tol_fun;     /* 1e-8  */
+    int max_iter;       /* those of ba_lm_params_default */
+    int max_fun_ev;
+    int max_trials;     /* stop after this many table rows (0 = unlimited) */
+    int verbose;
+} ba_dogleg_params;
+void ba_dogleg_params_default(ba_dogleg_params *p);
+int ba_minimize_dogleg(ba_solver *s, const ba_dogleg_params *p, ba_trial_cb cb, void *user, ba_result *out);
 
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);

@@ -53,7 +53,11 @@ EXPORTS = [
     "ba_solver_set_damping", "ba_solver_get_damping",
     "ba_solver_set_pcg_model_tol", "ba_solver_pcg_stop_stats",
     "ba_dogleg_coefficients", "ba_solver_dogleg_prepare", "ba_solver_try_dogleg", "ba_dogleg_params_default", "ba_minimize_dogleg",
+    "ba_triangulate_params_default", "ba_solver_triangulate_points", "ba_triangulate_point",
 ]
+# ba_triangulate_status (include/ba_mi355x.h)
+TRI_REPLACED, TRI_FEW_VIEWS, TRI_LOW_ANGLE, TRI_DEGENERATE, TRI_BEHIND, TRI_REPROJ, TRI_NOT_BETTER, TRI_FIXED = range(8)
+TRI_NAMES = ("REPLACED", "FEW_VIEWS", "LOW_ANGLE", "DEGENERATE", "BEHIND", "REPROJ", "NOT_BETTER", "FIXED")
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
 
@@ -106,6 +110,33 @@ class DoglegParams(C.Structure):
         p = cls()
         lib().ba_dogleg_params_default(C.byref(p))
         return p
+
+
+class TriangulateParams(C.Structure):
+    _fields_ = [("min_angle_deg", C.c_double), ("max_reproj_px", C.c_double), ("refine_iters", C.c_int), ("only_if_better", C.c_int)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        lib().ba_triangulate_params_default(C.byref(p))
+        return p
+
+
+class TriangulateStats(C.Structure):
+    _fields_ = [("asked", C.c_longlong), ("by_status", C.c_longlong * 8), ("cost_before", C.c_double), ("cost_after", C.c_double),
+                ("ms", C.c_double)]
+
+
+def _tri_params(min_angle_deg, max_reproj_px, refine_iters, only_if_better):
+    tp = TriangulateParams.default()
+    if min_angle_deg is not None:
+        tp.min_angle_deg = float(min_angle_deg)
+    if max_reproj_px is not None:
+        tp.max_reproj_px = float(max_reproj_px)
+    if refine_iters is not None:
+        tp.refine_iters = int(refine_iters)
+    tp.only_if_better = int(bool(only_if_better))
+    return tp
 
 
 TRIAL_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double)
@@ -178,6 +209,10 @@ def lib():
         L.ba_dogleg_params_default.restype = None
         L.ba_dogleg_params_default.argtypes = [C.c_void_p]
         L.ba_minimize_dogleg.argtypes = [C.c_void_p] * 5
+        L.ba_triangulate_params_default.restype = None
+        L.ba_triangulate_params_default.argtypes = [C.c_void_p]
+        L.ba_solver_triangulate_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.ba_triangulate_point.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_double] + [C.c_void_p] * 7
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_constant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_problem_gauge_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -421,6 +456,21 @@ class Solver:
         out = dict(status=res.status, iterations=res.iterations, trials=res.trials, fun_evals=res.fun_evals, energy=res.energy,
                    radius=res.lambda_, seconds=res.seconds, schur_ms=res.schur_ms, linearize_ms=res.linearize_ms)
         return out, np.array(rows).reshape(-1, 6)
+
+    # -- triangulation (every kind, one shard; include/ba_mi355x.h) ---------------------------------------------
+    def triangulate_points(self, points=None, min_angle_deg=None, max_reproj_px=None, refine_iters=None, only_if_better=True):
+        """ba_solver_triangulate_points on the resident state for `points` (problem numbering; None = all): (stats dict with asked,
+        by_status [8], cost_before, cost_after, ms; status uint8 per asked point, TRI_*).  None keeps a default of
+        ba_triangulate_params_default.  A linearize() comes next."""
+        tp = _tri_params(min_angle_deg, max_reproj_px, refine_iters, only_if_better)
+        ids = None if points is None else np.ascontiguousarray(points, np.int32).reshape(-1)
+        n = self.problem.M if ids is None else len(ids)
+        status = np.zeros(max(n, 1), np.uint8)
+        ts = TriangulateStats()
+        _chk(lib().ba_solver_triangulate_points(self._h, C.byref(tp), 0 if ids is None else n, None if ids is None else _p(ids), _p(status),
+                                                C.byref(ts)), "ba_solver_triangulate_points")
+        return (dict(asked=ts.asked, by_status=np.array(list(ts.by_status), np.int64), cost_before=ts.cost_before,
+                     cost_after=ts.cost_after, ms=ts.ms), status[:n])
 
     def timing(self, reset=False):
         t = Timing()
@@ -725,6 +775,26 @@ def dogleg_coefficients(g2, q, gn2, g_dot_gn, mu, radius):
     _chk(lib().ba_dogleg_coefficients(float(g2), float(q), float(gn2), float(g_dot_gn), float(mu), float(radius), C.byref(a), C.byref(c),
                                       C.byref(b), C.byref(pr)), "ba_dogleg_coefficients")
     return a.value, c.value, b.value, pr.value
+
+
+def triangulate_point(cam15, meas, x_old, w=None, loss_kind=LOSS_REFERENCE, loss_scale=0.5, min_angle_deg=None, max_reproj_px=None,
+                      refine_iters=None, only_if_better=True):
+    """ba_triangulate_point (host only): the per-point rule on one track.  cam15 [t, 15] (rows of GET_CAMS, one per observation),
+    meas [t, 2], w [t] or None: dict(x, status, cost_old, cost_new, angle_deg).  Raises BAError (ERR_ARG) for what the library refuses."""
+    cam15 = np.ascontiguousarray(cam15, np.float64).reshape(-1, 15)
+    t = len(cam15)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 2)
+    x_old = np.ascontiguousarray(x_old, np.float64).reshape(3)
+    if len(meas) != t or (w is not None and np.size(w) != t):
+        raise ValueError("cam15, meas and w disagree on the track length")
+    ww = None if w is None else np.ascontiguousarray(w, np.float64).reshape(-1)
+    tp = _tri_params(min_angle_deg, max_reproj_px, refine_iters, only_if_better)
+    x = np.zeros(3)
+    st, c0, c1, ang = C.c_int(), C.c_double(), C.c_double(), C.c_double()
+    _chk(lib().ba_triangulate_point(t, _p(cam15) if t else None, _p(meas) if t else None, None if ww is None or not t else _p(ww),
+                                    int(loss_kind), float(loss_scale), C.byref(tp), _p(x_old), _p(x), C.byref(st), C.byref(c0), C.byref(c1),
+                                    C.byref(ang)), "ba_triangulate_point")
+    return dict(x=x, status=st.value, cost_old=c0.value, cost_new=c1.value, angle_deg=ang.value)
 
 
 def relative_pose(cam15, a, b):

@@ -123,6 +123,10 @@ void ba_plan_relpose_csr(int N, int n, const int *pairs, std::vector<int> &ptr, 
 // owner-packed buffer of `world` chunks of equal length, in units of nb scalars.  Returns that length (scalars): the largest fill.
 size_t ba_plan_owner_offsets(int Dp, int nb, int world, std::vector<int> &off);
 
+// ba_solver_triangulate_points' and ba_triangulate_point's common refusals (ba_triangulate.cpp): BA_ERR_ARG for min_angle_deg outside
+// [0, 180), max_reproj_px < 0, refine_iters < 0 or a value that is not finite
+int ba_triangulate_params_check(const ba_triangulate_params *p);
+
 // RCCL transport (ba_comm.cpp); comm is an ncclComm_t
 int ba_rccl_init(void **comm_out, const void *id128, int rank, int world);
 void ba_rccl_destroy(void *comm);

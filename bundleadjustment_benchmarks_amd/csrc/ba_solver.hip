@@ -17,6 +17,7 @@
 #include "ba_prior.hip.h"
 #include "ba_relpose.hip.h"
 #include "ba_dogleg.hip.h"
+#include "ba_triangulate.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -115,6 +116,7 @@ struct SolverBase {
     virtual int dogleg_prepare(double mu, ba_dogleg_info *out) = 0;
     virtual int try_dogleg(double radius, double *e_test, double *pred, double *dx_norm, int *branch) = 0;
     virtual int minimize_dogleg(const ba_dogleg_params *dp, ba_trial_cb cb, void *user, ba_result *out) = 0;
+    virtual int triangulate(const ba_triangulate_params *p, int n_pts, const int *pt_ids, unsigned char *status, ba_triangulate_stats *stats) = 0;
     virtual int stats(double *out4) = 0;
     virtual int get(int what, double *out, size_t n) = 0;
     virtual int set_state(const double *cam15, const double *pts) = 0;
@@ -609,6 +611,7 @@ template <typename T> struct Solver final : SolverBase {
         dl_valid = false;  // (and so is a prepared dogleg)
         if ((rc = linearize_enqueue(diag_max != nullptr, nullptr))) return rc;
         mask_pending = false; // (J, g and the records are now the current mask's)
+        model_pending = false;
         if (more_qr() && (rc = more_outer_finish(nullptr))) return rc;
         if (sharded()) { // the kernels left this shard's part in SC_ELOC (it also rides on the next trial's packed all-reduce)
             HIPCHK(hipMemcpyAsync(d_scal.p + SC_ENERGY, d_scal.p + SC_ELOC, sizeof(T), hipMemcpyDeviceToDevice, st));
@@ -1355,7 +1358,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg_part_s) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + bytes_of(d_dl_keep) + bytes_of(d_dl_part) + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
+               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + bytes_of(d_dl_keep) + bytes_of(d_dl_part) + tri_bytes() + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1755,7 +1758,8 @@ template <typename T> struct Solver final : SolverBase {
     DevBuf<unsigned short> d_cmask; // [N]
     DevBuf<unsigned char> d_pfix;   // [Ml] of this shard
     bool masked = false;
-    bool mask_pending = false; // a mask or a measurement model set since the last linearisation: J is the old one's, try_step refuses
+    bool mask_pending = false; // a mask or a measurement model set, or points re-seated by triangulate(), since the last linearisation: J is
+                               // the old one's, try_step refuses
     int set_constant(const unsigned short *cm, const unsigned char *pf) override
     {
         bool any = false, all = sx.M > 0 || N > 0;
@@ -1819,6 +1823,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipStreamSynchronize(st));
         loss_kind = kind;
         loss_scale = (T)scale;
+        model_pending = true;
         return model_changed();
     }
     int set_obs_weights(const double *w) override
@@ -1834,6 +1839,7 @@ template <typename T> struct Solver final : SolverBase {
             if (!d_wobs.p && (rc = d_wobs.alloc(hw.size()))) return rc;
             HIPCHK(hipMemcpy(d_wobs.p, hw.data(), sizeof(T) * hw.size(), hipMemcpyHostToDevice));
         }
+        model_pending = true;
         return model_changed();
     }
 
@@ -2361,6 +2367,96 @@ template <typename T> struct Solver final : SolverBase {
             out->linearize_ms = nl ? (tm.linearize_ms - tm0.linearize_ms) / nl : 0.0;
         }
         return rc;
+    }
+
+    // ---- triangulation (ba_solver_triangulate_points; ba_triangulate.hip.h) -------------------------------------
+    // Buffers of its own, all allocated by the first call: the rays [3][Kl] fp64, status / request / fixed flags [Ml] each, and one fp64
+    // buffer [block partials: 10 tri_gmax() | the ten sums, padded to 16].
+    DevBuf<double> d_tri_ray, d_tri_part;
+    DevBuf<int> d_tri_ids;
+    DevBuf<unsigned char> d_tri_stat, d_tri_fix;
+    bool model_pending = false; // ba_solver_set_loss / _set_obs_weights since the last linearisation
+    enum { TRI_LANES = 8, TRI_NSUM = 10 };
+    int tri_gmax() const { return std::max(1, (int)(((size_t)Ml * TRI_LANES + 255) / 256)); }
+    size_t tri_bytes() const { return bytes_of(d_tri_ray) + bytes_of(d_tri_part) + bytes_of(d_tri_ids) + bytes_of(d_tri_stat) + bytes_of(d_tri_fix); }
+
+    int triangulate(const ba_triangulate_params *pp, int n_pts, const int *pt_ids, unsigned char *status, ba_triangulate_stats *stats) override
+    {
+        ba_triangulate_params tp;
+        if (pp) tp = *pp; else ba_triangulate_params_default(&tp);
+        if (sharded() || ba_triangulate_params_check(&tp) || n_pts < 0 || (!pt_ids && n_pts > 0) || model_pending) return BA_ERR_ARG;
+        const int n = pt_ids ? n_pts : Ml;
+        if (n > Ml) return BA_ERR_ARG; // (some id is listed twice)
+        if (pt_ids) {
+            std::vector<char> seen((size_t)(Ml > 0 ? Ml : 1), 0);
+            for (int q = 0; q < n; q++) {
+                if (pt_ids[q] < 0 || pt_ids[q] >= Ml || seen[pt_ids[q]]) return BA_ERR_ARG;
+                seen[pt_ids[q]] = 1;
+            }
+        }
+        int rc;
+        if (!d_tri_part.p) { // everything that can fail first: the solver is unchanged behind an error
+            DevBuf<double> nr, np;
+            DevBuf<int> ni;
+            DevBuf<unsigned char> ns, nf;
+            const size_t m1 = (size_t)(Ml > 0 ? Ml : 1);
+            if ((rc = nr.alloc((size_t)3 * (Kl > 0 ? Kl : 1))) || (rc = np.alloc((size_t)TRI_NSUM * tri_gmax() + 16)) || (rc = ni.alloc(m1)) ||
+                (rc = ns.alloc(m1)) || (rc = nf.alloc(m1))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(np.p, 0, sizeof(double) * np.n));
+            d_tri_ray.swap(nr); d_tri_part.swap(np); d_tri_ids.swap(ni); d_tri_stat.swap(ns); d_tri_fix.swap(nf);
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        ba_triangulate_stats ts{};
+        ts.asked = n;
+        if (n > 0) {
+            // a point held constant or carrying a prior is never touched
+            const bool any_fix = (masked && d_pfix.p) || n_pr[0] > 0;
+            if (any_fix) {
+                std::vector<unsigned char> hf((size_t)Ml, 0);
+                if (masked && d_pfix.p) HIPCHK(hipMemcpy(hf.data(), d_pfix.p, (size_t)Ml, hipMemcpyDeviceToHost));
+                if (n_pr[0] > 0) {
+                    std::vector<int> hid((size_t)n_pr[0]);
+                    HIPCHK(hipMemcpy(hid.data(), d_pr_id[0].p, sizeof(int) * hid.size(), hipMemcpyDeviceToHost));
+                    for (int id : hid) hf[id] = 1;
+                }
+                HIPCHK(hipMemcpy(d_tri_fix.p, hf.data(), hf.size(), hipMemcpyHostToDevice));
+            }
+            if (pt_ids) HIPCHK(hipMemcpy(d_tri_ids.p, pt_ids, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+            const int *ids = pt_ids ? (const int *)d_tri_ids.p : nullptr;
+            const int g = (int)(((size_t)n * TRI_LANES + 255) / 256);
+            const ba_tri_cfg cf{tp.min_angle_deg * (M_PI / 180.0), tp.max_reproj_px, tp.refine_iters, tp.only_if_better, loss_kind, (double)loss_scale};
+            double *sums = d_tri_part.p + (size_t)TRI_NSUM * tri_gmax();
+            HIPCHK(hipEventRecord(ev[EV_T0], st));
+            hipLaunchKernelGGL((k_tri_rays<T, TRI_LANES>), dim3(g), dim3(256), 0, st, n, ids, N, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
+                               (const T *)d_cam[0].p, (const T *)d_meas.p, d_tri_ray.p);
+            hipLaunchKernelGGL((k_tri_points<T, TRI_LANES>), dim3(g), dim3(256), 0, st, n, ids, N, Ml, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
+                               (const T *)d_cam[0].p, (const T *)d_meas.p, (const T *)d_wobs.p, (const double *)d_tri_ray.p,
+                               any_fix ? (const unsigned char *)d_tri_fix.p : (const unsigned char *)nullptr, cf, d_pts[0].p, d_tri_stat.p, d_tri_part.p);
+            ba_red_jobs jobs{};
+            for (int k = 0; k < 8; k++) jobs.j[k] = {d_tri_part.p + (size_t)k * g, g, 0, k};
+            hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(8), dim3(256), 0, st, jobs, sums, (const int *)nullptr, (long long *)nullptr);
+            ba_red_jobs jobs2{};
+            for (int k = 0; k < 2; k++) jobs2.j[k] = {d_tri_part.p + (size_t)(8 + k) * g, g, 0, 8 + k};
+            hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(2), dim3(256), 0, st, jobs2, sums, (const int *)nullptr, (long long *)nullptr);
+            HIPCHK(hipEventRecord(ev[EV_T1], st));
+            double h[TRI_NSUM];
+            HIPCHK(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            if (status) HIPCHK(hipMemcpy(status, d_tri_stat.p, (size_t)n, hipMemcpyDeviceToHost));
+            for (int k = 0; k < 8; k++) ts.by_status[k] = (long long)h[k];
+            ts.cost_before = h[8]; ts.cost_after = h[9];
+            ts.ms = ev_ms(EV_T0, EV_T1);
+        }
+        // what ba_solver_set_state(s, NULL, pts) invalidates; and J is another state's: ba_solver_try_step refuses until the next
+        // linearisation, as it does behind a setter
+        cov_valid = false;
+        dl_valid = false;
+        have_lin = false;
+        have_step = false;
+        mask_pending = true;
+        if (stats) *stats = ts;
+        return BA_OK;
     }
 
     int stats(double *out4) override
@@ -3029,6 +3125,11 @@ int ba_solver_try_dogleg(ba_solver *s, double radius, double *energy_test, doubl
 int ba_minimize_dogleg(ba_solver *s, const ba_dogleg_params *p, ba_trial_cb cb, void *user, ba_result *out)
 {
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->minimize_dogleg(p, cb, user, out);
+}
+int ba_solver_triangulate_points(ba_solver *s, const ba_triangulate_params *p, int n_pts, const int *pt_ids, unsigned char *status,
+                                 ba_triangulate_stats *stats)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->triangulate(p, n_pts, pt_ids, status, stats);
 }
 int ba_solver_stats(ba_solver *s, double *out4) { return !(s && out4) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->stats(out4); }
 int ba_solver_get(ba_solver *s, int what, double *out, size_t n) { return !(s && out) ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->get(what, out, n); }

@@ -727,6 +727,68 @@ typedef struct {
 void ba_dogleg_params_default(ba_dogleg_params *p);
 int ba_minimize_dogleg(ba_solver *s, const ba_dogleg_params *p, ba_trial_cb cb, void *user, ba_result *out);
 
+/* ---- triangulation: re-seat points from the cameras that see them (no reference counterpart; COLMAP's retriangulation between
+ * bundle-adjustment rounds, Ceres and g2o pipelines' triangulation front ends) ---------------------------------- */
+
+/* Model: XX = R X + T, xu = XX_01 / XX_2, kr = 1 + k1 |xu|^2 + k2 |xu|^4, pi = f kr xu, with R, T, f, k1, k2 the 15 scalars of
+ * BA_GET_CAMS.  BAL's camera looks down -z: X is in front of camera a iff (R_a X + T_a)_2 < 0.  All geometry below is fp64 for both
+ * scalar types; it reads the resident state as stored, and the new point is rounded once to the solver's scalar type.
+ * The rule per point (csrc/ba_triangulate.hip.h, one text for the host function and the kernel), over its t observations o:
+ * 1. Undistort: m = meas_o / f; rho solves rho (1 + k1 rho^2 + k2 rho^4) = |m| by 12 Newton steps from rho = |m|; xu = m rho / |m|
+ *    (0 when |m| = 0).  The observation is UNUSABLE if a derivative 1 + 3 k1 rho^2 + 5 k2 rho^4 met on the way or at the end is <= 0, a
+ *    value is not finite, rho ends <= 0, or the equation is missed by more than 1e-12 |m|.  Ray d_o = R' (-(xu, 1)) normalised, centre
+ *    C_o = -R'T.
+ * 2. theta = the largest angle between two usable rays, from the largest chord: theta = 2 atan2(c, sqrt(4 - c^2)), c = max |d_i - d_j|.
+ *    Fewer than two usable observations: BA_TRI_FEW_VIEWS.  theta < min_angle_deg: BA_TRI_LOW_ANGLE.
+ * 3. Midpoint: X minimises sum_o w_o^2 |(I - d_o d_o')(X - C_o)|^2 over the usable observations (w_o: ba_solver_set_obs_weights, else 1),
+ *    a 3 x 3 Cholesky; a pivot <= 0 or not finite: BA_TRI_DEGENERATE.
+ * 4. refine_iters monotone IRLS Gauss-Newton steps on the point's own term c(X) = sum_o rho(s_o), s_o = w_o^2 |pi_o(X) - meas_o|^2, rho the
+ *    loss in force, over ALL its observations: H = sum rho'(s_o) J_o'J_o, g = sum rho'(s_o) J_o'r_o (r_o = w_o (pi_o - meas_o), J_o its
+ *    derivative by X), mu = 1e-9 tr(H) / 3, X' = X - (H + mu I)^-1 g, taken iff c(X') < c(X) (1 - 1e-11) -- a decrease that an fp64
+ *    evaluation of c can tell from rounding; a plain c(X') < c(X) would let the order of a sum decide the last step --; otherwise, or
+ *    when a pivot of H + mu I is <= 0, the refinement stops.  rho' = 1 (TRIVIAL), (1 - s / tau^2) / 2 below tau^2 and 0 above (REFERENCE), 1 up to delta^2 and
+ *    delta / sqrt(s) above (HUBER), 1 / (1 + s / c^2) (CAUCHY).
+ * 5. The candidate must lie in front of every camera of the track, else BA_TRI_BEHIND; with max_reproj_px > 0 every usable observation
+ *    must have an unweighted |pi - meas| <= max_reproj_px, else BA_TRI_REPROJ; with only_if_better c(X_new) < c(X_old) is required,
+ *    else BA_TRI_NOT_BETTER.  A point held constant by ba_solver_set_constant or carrying a point prior is BA_TRI_FIXED and never
+ *    touched; a point nobody observes is BA_TRI_FEW_VIEWS.  BA_TRI_REPLACED = 0: the resident point takes X_new.  Any other status keeps
+ *    the point's bits.
+ * Sums over a track: the host function adds in observation order; the kernel gives a point 8 lanes of a wavefront, lane l adds the
+ * observations l, l + 8, ... in order and the lanes are combined by a fixed butterfly: a point's result and status are the same bits on
+ * every run, whatever else is in the request and wherever the point stands in it.  No atomics. */
+typedef enum {
+    BA_TRI_REPLACED = 0, BA_TRI_FEW_VIEWS = 1, BA_TRI_LOW_ANGLE = 2, BA_TRI_DEGENERATE = 3, BA_TRI_BEHIND = 4, BA_TRI_REPROJ = 5,
+    BA_TRI_NOT_BETTER = 6, BA_TRI_FIXED = 7
+} ba_triangulate_status;
+typedef struct { double min_angle_deg; double max_reproj_px; int refine_iters; int only_if_better; } ba_triangulate_params;
+void ba_triangulate_params_default(ba_triangulate_params *p); /* 1.5 (COLMAP's min_tri_angle), 0 = off, 5, 1 */
+/* cost_before / cost_after: sum of c(X) over the asked points before the call and behind it (a refused point counts its old c twice),
+ * fp64, block partials of 32 points reduced in a fixed order; ms: device time of the call's launches. */
+typedef struct { long long asked, by_status[8]; double cost_before, cost_after; double ms; } ba_triangulate_stats;
+/* ba_solver_triangulate_points: the rule for the points pt_ids[0 .. n_pts) (PROBLEM numbering), or for all M points when pt_ids is NULL
+ * and n_pts is 0, on the resident state x.  status (may be NULL) receives one byte per asked point in the order of the request (M bytes
+ * for all points); stats may be NULL; p == NULL means the defaults.  Every solver kind, BA_F64 and BA_F32, shard_world == 1.
+ * A successful call invalidates what ba_solver_set_state(s, NULL, pts) invalidates -- the linearisation, a pending step, a computed
+ * covariance, a prepared dogleg -- and, J being another state's, ba_solver_try_step returns BA_ERR_ARG until the next
+ * ba_solver_linearize or ba_minimize, as it does behind a setter.  It leaves the cameras, xTest, masks, priors, groups and captured
+ * graphs alone.  With no point replaced the state keeps every bit.
+ * BA_ERR_ARG, decided on the host, the solver unchanged: a sharded solver (not built); an id out of range or listed twice; n_pts < 0;
+ * pt_ids NULL with n_pts > 0; min_angle_deg outside [0, 180), max_reproj_px < 0, refine_iters < 0 or any of them not finite; a
+ * ba_solver_set_loss or ba_solver_set_obs_weights call that no ba_solver_linearize or ba_minimize has followed (which loss is "in
+ * force" would be ambiguous).
+ * Memory, allocated by the first call, kept until ba_solver_free and counted by ba_solver_device_bytes:
+ *   24 K (the rays) + 6 M (status, request, fixed flags: 1 + 4 + 1) + 8 (10 max(1, ceil(8 M / 256)) + 16) bytes.
+ * BA_ERR_NOMEM when they do not fit; the solver stays usable. */
+int ba_solver_triangulate_points(ba_solver *s, const ba_triangulate_params *p, int n_pts, const int *pt_ids, unsigned char *status,
+                                 ba_triangulate_stats *stats);
+/* ba_triangulate_point: the rule on one track, host only (no GPU).  cam15: 15 t (one BA_GET_CAMS row per observation), meas: 2 t,
+ * w: t or NULL.  x_new receives the candidate where the rule formed one (statuses 0, 4, 5, 6) and x_old otherwise; cost_new its c,
+ * or c(x_old); angle_deg theta (0 with fewer than two usable observations).  Any output pointer may be NULL; p == NULL: the defaults.
+ * BA_ERR_ARG: t < 0, a missing array, parameters as above, an unknown loss, a scale or weight that is not positive and finite. */
+int ba_triangulate_point(int t, const double *cam15, const double *meas, const double *w, int loss_kind, double loss_scale,
+                         const ba_triangulate_params *p, const double *x_old, double *x_new, int *status, double *cost_old,
+                         double *cost_new, double *angle_deg);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);

@@ -70,9 +70,15 @@ template <typename F> void with_flags(bool a, bool b, F &&f)
 }
 template <int V> using int_c = std::integral_constant<int, V>; // (a template argument that is not a flag: k_eval's FUSE)
 
+// Owns its device memory: movable (the source is left empty), not copyable
 template <typename T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; } // (frees what it held)
     int alloc(size_t count)
     {
         n = count;
@@ -102,10 +108,10 @@ template <typename T> struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr; n = 0;
     }
-    // a setter stages its new lists in locals and commits them by swapping: the old ones leave with the locals
-    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
     ~DevBuf() { release(); }
 };
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value); static_assert(!std::is_copy_assignable<DevBuf<int>>::value);
+template <typename B> size_t bytes_of(const B &b) { return b.p ? sizeof(*b.p) * b.n : 0; }
 
 struct SolverBase {
     virtual ~SolverBase() {}
@@ -255,7 +261,6 @@ template <typename T> struct Solver final : SolverBase {
     int gE = 0;
     bool fuse = false;
     DevBuf<int> d_eb;
-    bool have_step = false;
     bool step_level = false; // inside try_step: the segments add the phase events, the kept S, the QR self-check and their own test-energy sum
     int num_cus = 256; // of the device the solver lives on
     double wall_khz = 1e5;
@@ -267,6 +272,121 @@ template <typename T> struct Solver final : SolverBase {
     int fault_rowflag = 0;    // self-test (2): the fused steps' row workgroups stay silent, the panel's wait is short
     double spin_next_s = 0;   // self-test (3): a kernel of that many seconds in front of the next trial
     double watchdog_s = 600;  // no LM row for that long = a hung launch (BA_WATCHDOG_S)
+
+    // ---- the state of the optional features: one struct each, as Forest `fo` and Share `sh` further down ------------------------------
+    // A struct holds its feature's buffers, counts and flags and sums its bytes.  A setter or a first-use allocator fills a new one --
+    // everything that can fail -- and commits it with one move: the solver is unchanged behind any error, the old buffers leave there.
+    struct Mask { // ba_solver_set_constant
+        DevBuf<unsigned short> cmask; // [N]
+        DevBuf<unsigned char> pfix;   // [Ml] of this shard
+        bool on = false;              // some bit is set: the masked instantiations
+        size_t bytes() const { return bytes_of(cmask) + bytes_of(pfix); }
+    } mk;
+    struct Model { // ba_solver_set_loss / ba_solver_set_obs_weights
+        int loss_kind = BA_LOSS_REFERENCE;
+        T loss_scale = (T)0.5;
+        DevBuf<T> wobs; // [Kl] of this shard, the solver's observation order (like d_meas)
+        size_t bytes() const { return bytes_of(wobs); }
+    } md;
+    struct PriorList { // one type's compact lists: what a call of ba_solver_set_point_priors / _centre_priors / _intrinsics_priors replaces
+        DevBuf<int> id;
+        DevBuf<T> x0, info;
+        int n = 0;
+        size_t bytes() const { return bytes_of(id) + bytes_of(x0) + bytes_of(info); }
+    };
+    struct Priors {
+        PriorList of[3];    // 0 points (info = L, 9 per prior), 1 centres (L), 2 intrinsics (info = w, 3 per prior)
+        DevBuf<int> lonely; // the points with a prior and no observation (k_prior_lonely)
+        DevBuf<T> part;     // [3][g] prior energies of the last linearisation
+        int g = 0;          // workgroups of k_prior
+        size_t bytes() const { return of[0].bytes() + of[1].bytes() + of[2].bytes() + bytes_of(lonely) + bytes_of(part); }
+    } pr;
+    struct RelPoses { // ba_solver_set_relative_poses: the lists, the per-constraint records, the CSR of every camera's incident constraints
+        DevBuf<int> pair, ptr, inc;
+        DevBuf<T> R0, t0, Lr, Lt, rec, part; // part: [2][g] energies of the last linearisation
+        int n = 0, g = 0;                    // g: workgroups of k_relpose
+        std::vector<int> h_pair;             // the constraint list as set (host copy for the forest)
+        size_t bytes() const { return bytes_of(pair) + bytes_of(ptr) + bytes_of(inc) + bytes_of(R0) + bytes_of(t0) + bytes_of(Lr) + bytes_of(Lt) + bytes_of(rec) + bytes_of(part); }
+    } rp;
+    struct Dogleg { // allocated by the first ba_solver_dogleg_prepare
+        DevBuf<T> keep;        // the copy of dx_gn [3 Ml + D]
+        DevBuf<double> part;   // [q partials: gK | g2, gn2, g'dx_gn partials: 3 dl_gd() | |dx|^2 partials: gM + 1 | the eight sums]
+        ba_dogleg_info info{}; // the scalars of the last prepare
+        size_t bytes() const { return bytes_of(keep) + bytes_of(part); }
+    } dg;
+    struct Triang { // allocated by the first ba_solver_triangulate_points
+        DevBuf<double> ray, part;        // the rays [3][Kl]; [block partials: 10 tri_gmax() | the ten sums, padded to 16]
+        DevBuf<int> ids;                 // [Ml] the request
+        DevBuf<unsigned char> stat, fix; // [Ml] each
+        size_t bytes() const { return bytes_of(ray) + bytes_of(part) + bytes_of(ids) + bytes_of(stat) + bytes_of(fix); }
+    } tr;
+    struct Cov { // allocated by the first ba_solver_covariance_compute
+        DevBuf<T> buf; // the work buffer (cov_wp() ... cov_count() below)
+        DevBuf<int> flag;
+        double lambda = 0, ms[4] = {0, 0, 0, 0};
+        size_t bytes() const { return bytes_of(buf) + bytes_of(flag); }
+    } cv;
+
+    // ---- what is valid: six flags, written by these transitions alone (entry point x flag: the table in DESIGN.md section 1) ----------
+    struct Valid {
+        bool have_lin = false;      // a linearisation at x exists
+        bool have_step = false;     // xTest is the step of a trial: ba_solver_accept may take it
+        bool cov_valid = false;     // ba_solver_covariance_get may return the computed blocks
+        bool dl_valid = false;      // a prepared dogleg of the linearisation in place
+        bool mask_pending = false;  // a setter or triangulate() since the last linearisation: J is the old one's, try_step refuses
+        bool model_pending = false; // ba_solver_set_loss / _set_obs_weights since the last linearisation: triangulate() refuses
+        void results_dropped() { cov_valid = false; dl_valid = false; } // (a covariance, a prepared dogleg: of the linearisation they came from)
+        void lin_dropped() { results_dropped(); have_lin = false; }     // J is another state's
+        void step_dropped() { have_step = false; }
+        void stepped() { have_step = true; }
+        void accepted() { step_dropped(); }                             // x = xTest has happened
+        void x_moved() { lin_dropped(); step_dropped(); }               // behind a driver: a ba_solver_linearize at the final x comes first
+        void points_reseated() { x_moved(); mask_pending = true; }      // what set_state(NULL, pts) drops, and try_step refuses as behind a setter
+        void model_changed(bool measurement) { results_dropped(); step_dropped(); mask_pending = true; model_pending = model_pending || measurement; }
+        void pending_taken() { mask_pending = false; model_pending = false; } // J, g and the records are now the current mask's and model's
+        void linearised() { have_lin = true; }
+        void cov_dropped() { cov_valid = false; }
+        void cov_computed() { cov_valid = true; }
+        void dogleg_dropped() { dl_valid = false; }
+        void dogleg_prepared() { dl_valid = true; }
+    } vf;
+
+    // ---- the block partials the second-stage sums read, their layout stated here alone ----------------------------------------------
+    // d_part_e  = [gE of k_eval | 3 gP of k_prior | 2 gR of k_relpose]: energies, summed in this fixed order (gP = pr.g, gR = rp.g)
+    // d_part_pm = [gM of k_point_prep | gP of k_prior]: point diagonals (behind the points' own: the ones a point prior has raised)
+    size_t part_e_count(int gp, int gr) const { return (size_t)gE + 3 * (size_t)gp + 2 * (size_t)gr; }
+    size_t part_pm_count(int gp) const { return (size_t)gM + (size_t)gp; }
+    int part_e_n() const { return (int)part_e_count(pr.g, rp.g); }
+    int part_pm_n() const { return (int)part_pm_count(pr.g); }
+    T *part_e_priors() const { return d_part_e.p + part_e_count(0, 0); }
+    T *part_e_relposes() const { return d_part_e.p + part_e_count(pr.g, 0); }
+    T *part_pm_priors() const { return d_part_pm.p + part_pm_count(0); }
+    // both buffers anew, zero-filled, for (gP, gR): the last step of a setter that can fail, directly in front of its commit
+    int resize_partials(int gp, int gr)
+    {
+        DevBuf<T> ne, nm;
+        int rc;
+        if ((rc = ne.alloc(part_e_count(gp, gr))) || (rc = nm.alloc(part_pm_count(gp)))) { (void)hipGetLastError(); return rc; }
+        HIPCHK(hipMemset(ne.p, 0, sizeof(T) * ne.n));
+        HIPCHK(hipMemset(nm.p, 0, sizeof(T) * nm.n));
+        d_part_e = std::move(ne); d_part_pm = std::move(nm);
+        return BA_OK;
+    }
+
+    // ---- argument checks the setters share --------------------------------------------------------------------------------------------
+    // finite as doubles and in the solver's scalar type
+    static bool finite_in_T(const double *v, size_t cnt) { return std::all_of(v, v + cnt, [](double x) { return std::isfinite(x) && std::isfinite((T)x); }); }
+    static bool positive_in_T(double v) { return v > 0 && std::isfinite(v) && (T)v > 0 && std::isfinite((T)v); } // (a NaN fails the comparisons)
+    static bool distinct_ids(int n, const int *ids, int lim) // n ids in [0, lim), none listed twice
+    {
+        if (n > lim) return false;
+        std::vector<char> seen((size_t)(lim > 0 ? lim : 1), 0);
+        for (int q = 0; q < n; q++) {
+            if (ids[q] < 0 || ids[q] >= lim || seen[ids[q]]) return false;
+            seen[ids[q]] = 1;
+        }
+        return true;
+    }
 
     ~Solver() override
     {
@@ -446,7 +566,7 @@ template <typename T> struct Solver final : SolverBase {
             if ((rc = d_ldlt_jobs.upload(ldlt_plan.jobs))) return rc;
             ldlt_plan.d_jobs = d_ldlt_jobs.p;
         }
-        AL(d_part_e, (size_t)gE); AL(d_part_pm, (size_t)gM);
+        AL(d_part_e, part_e_count(0, 0)); AL(d_part_pm, part_pm_count(0));
         AL(d_part_bs, (size_t)2 * gB); AL(d_part_st, (size_t)4 * gK); AL(d_scal, NSCAL);
 #undef AL
         if (d_S.p) HIPCHK(hipMemset(d_S.p, 0, sizeof(T) * d_S.n));
@@ -524,13 +644,13 @@ template <typename T> struct Solver final : SolverBase {
     // fused (with jac): the point part of the gradient and, CHOLESKY, the next trial's elimination in the same pass (k_eval<T, true, FUSE>)
     void launch_eval(bool jac, int which, const int *go = nullptr, bool commit = false, bool fused = false)
     {
-        const T tau2 = loss_scale * loss_scale; // (the square of the loss's scale: tau^2 of the reference's psi by default)
+        const T tau2 = md.loss_scale * md.loss_scale; // (the square of the loss's scale: tau^2 of the reference's psi by default)
         ba_fuse_args<T> fa{};
         fa.eb = d_eb.p; // (nullptr when a point has more than 256 observations: plain runs of 256)
         fa.pt_ptr = d_pt_ptr.p; fa.lam = d_scal.p + SC_LAMBDA; fa.U0 = d_U0.p; fa.gp = d_gp.p;
         fa.rec = d_rec.p; fa.dinv = d_dinv.p; fa.tvec = d_tvec.p; fa.tri = d_tri.p; fa.fresh = &d_lm.p->rec_fresh;
-        fa.cmask = d_cmask.p; fa.pfix = d_pfix.p;
-        fa.wobs = d_wobs.p; fa.loss = loss_kind; fa.lscale = loss_scale;
+        fa.cmask = mk.cmask.p; fa.pfix = mk.pfix.p;
+        fa.wobs = md.wobs.p; fa.loss = md.loss_kind; fa.lscale = md.loss_scale;
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
         // eval_coop: the fused CHOLESKY linearisation stores its records a wavefront's run at a time (FUSE = 3 in place of 2) -- except in
         // fp32 on a problem of one round of workgroups, where it measured 2 % slower than the owners' stores (profiles/EXPERIMENTS.md, 7)
@@ -544,7 +664,7 @@ template <typename T> struct Solver final : SolverBase {
         // model(): the instantiations of the general measurement model (ba_solver_set_loss / ba_solver_set_obs_weights); the reference's
         // psi at 0.5 px without weights stays on the kernels it always ran
         auto linearisation = [&](auto FUSE, auto SOA) {
-            with_flags(masked, model(), [&](auto MASK, auto MODEL) { launch(std::true_type{}, FUSE, SOA, MASK, MODEL); });
+            with_flags(mk.on, model(), [&](auto MASK, auto MODEL) { launch(std::true_type{}, FUSE, SOA, MASK, MODEL); });
         };
         constexpr std::false_type aos{};
         constexpr std::true_type soa{};
@@ -607,11 +727,9 @@ template <typename T> struct Solver final : SolverBase {
     int linearize(double *energy, double *diag_max) override
     {
         int rc;
-        cov_valid = false; // (a covariance is that of the linearisation it was computed from)
-        dl_valid = false;  // (and so is a prepared dogleg)
+        vf.results_dropped();
         if ((rc = linearize_enqueue(diag_max != nullptr, nullptr))) return rc;
-        mask_pending = false; // (J, g and the records are now the current mask's)
-        model_pending = false;
+        vf.pending_taken();
         if (more_qr() && (rc = more_outer_finish(nullptr))) return rc;
         if (sharded()) { // the kernels left this shard's part in SC_ELOC (it also rides on the next trial's packed all-reduce)
             HIPCHK(hipMemcpyAsync(d_scal.p + SC_ENERGY, d_scal.p + SC_ELOC, sizeof(T), hipMemcpyDeviceToDevice, st));
@@ -624,7 +742,7 @@ template <typename T> struct Solver final : SolverBase {
         tm.n_linearize++;
         if (energy) *energy = (double)h_scal[SC_ENERGY];
         if (diag_max) *diag_max = std::max((double)h_scal[SC_DMAX_P], (double)h_scal[SC_DMAX_C]);
-        have_lin = true;
+        vf.linearised();
         return BA_OK;
     }
 
@@ -639,7 +757,7 @@ template <typename T> struct Solver final : SolverBase {
         // energy sum rides on the last launch of launch_grad (no k_reduce_scalars launch) unless MOREQR's outer QR follows it
         ba_red_jobs jobs{};
         int nj = 0;
-        jobs.j[nj++] = {d_part_e.p, gE + 3 * gP + 2 * gR, 0, sharded() ? SC_ELOC : SC_ENERGY}; // (gP = 0 without priors, gR = 0 without constraints)
+        jobs.j[nj++] = {d_part_e.p, part_e_n(), 0, sharded() ? SC_ELOC : SC_ENERGY};
         const bool tail = go != nullptr && !want_dmax && kind != BA_MOREQR && !priors() && !relposes(); // (their energy partials come behind launch_grad)
         // behind a trial the point part of J^T r / J^T J and (CHOLESKY) the elimination of the next trial are part of the k_eval launch;
         // the first, host-synchronous linearisation (lambda0 is not known yet, max diag J^T J is wanted) keeps the separate launches
@@ -649,18 +767,18 @@ template <typename T> struct Solver final : SolverBase {
             launch_elim_qr(d_scal.p + SC_ZERO, d_rec0.p, d_dinv0.p, d_tvec0.p, d_tri0.p, go, /*thin Q for J2bot*/ more_qr());
             if (more_qr() && (rc = launch_more_outer(go))) return rc; // ... and the dense QR of J2bot(lambda = 0); its part 2 follows where a collective may stand
         }
-        if (tail) { have_step = false; return BA_OK; }
+        if (tail) { vf.step_dropped(); return BA_OK; }
         if (want_dmax) {
             // max diag(J^T J): point part per shard, camera part from the (summed over shards) diagonal of J_c^T J_c
             T *tmp = d_dxc.p;
             hipLaunchKernelGGL((k_vdiag<T>), dim3((D + 255) / 256), dim3(256), 0, st, N, d_V.p, tmp);
             if ((rc = allreduce(tmp, (size_t)D, 0))) return rc;
-            jobs.j[nj++] = {d_part_pm.p, gM + gP, 1, SC_DMAX_P}; // (behind the points' own: the diagonals a point prior has raised)
+            jobs.j[nj++] = {d_part_pm.p, part_pm_n(), 1, SC_DMAX_P};
             jobs.j[nj++] = {tmp, D, 1, SC_DMAX_C};
         }
         hipLaunchKernelGGL((k_reduce_scalars<T>), dim3(nj), dim3(256), 0, st, jobs, d_scal.p, go, &d_lm.p->t_end);
         if (!go) HIPCHK(hipEventRecord(ev[EV_L1], st));
-        have_step = false;
+        vf.step_dropped();
         return BA_OK;
     }
 
@@ -728,8 +846,8 @@ template <typename T> struct Solver final : SolverBase {
             });
         // every block of this S is written: the constraints' cross blocks join it here, for a trial and for the covariance alike
         if (relposes())
-            hipLaunchKernelGGL((k_relpose_schur<T>), dim3((unsigned)(((size_t)n_rp * 36 + 255) / 256)), dim3(256), 0, st, n_rp, (const int *)d_rp_pair.p,
-                               (const T *)d_rp_rec.p, ld, d_S.p);
+            hipLaunchKernelGGL((k_relpose_schur<T>), dim3((unsigned)(((size_t)rp.n * 36 + 255) / 256)), dim3(256), 0, st, rp.n, (const int *)rp.pair.p,
+                               (const T *)rp.rec.p, ld, d_S.p);
     }
 
     // ---- distributed factor (BA_DIST_FACTOR=1, sharded LDL^T symbols; SURVEY 8e "consider distributing K6" -- FUNCTIONAL, unmeasured: this
@@ -952,14 +1070,6 @@ template <typename T> struct Solver final : SolverBase {
         DevBuf<T> fac, u;
         DevBuf<double> work, part, xc, tpart;
         int ntrees = 0, nodes = 0, kept = 0, dropped = 0, largest = 0, width = 6;
-        void swap(Forest &o)
-        {
-            tree_ptr.swap(o.tree_ptr); node_cam.swap(o.node_cam); node_par.swap(o.node_par); node_rec.swap(o.node_rec); bad.swap(o.bad);
-            in_tree.swap(o.in_tree); fac.swap(o.fac); u.swap(o.u); work.swap(o.work); part.swap(o.part); edge_ptr.swap(o.edge_ptr);
-            edge_oo.swap(o.edge_oo); xc.swap(o.xc); tpart.swap(o.tpart);
-            std::swap(width, o.width);
-            std::swap(ntrees, o.ntrees); std::swap(nodes, o.nodes); std::swap(kept, o.kept); std::swap(dropped, o.dropped); std::swap(largest, o.largest);
-        }
         // partials of r'z behind the per-camera ones: one per tree, width 9 one per 256 trees (k_pcg_forest_rz)
         int nparts() const { return width == 9 ? (ntrees + 255) / 256 : ntrees; }
         size_t bytes() const
@@ -969,7 +1079,6 @@ template <typename T> struct Solver final : SolverBase {
         }
     } fo;
     int precond_kind = BA_PRECOND_BLOCK_JACOBI, precond_max_tree = BA_PCG_MAX_TREE_DEFAULT;
-    std::vector<int> h_rp_pair; // the constraint list as set (host copy for the forest)
     bool forest_on() const { return precond_kind != BA_PRECOND_BLOCK_JACOBI && fo.ntrees > 0; }
     ba_forest_dev<T> forest_dev() const
     {
@@ -979,12 +1088,12 @@ template <typename T> struct Solver final : SolverBase {
     // the forest's launches by the cross blocks' width
     void launch_forest_edges()
     {
-        hipLaunchKernelGGL((k_pcg_forest_edges<T>), dim3(fo.nodes), dim3(256), 0, st, forest_dev(), (const T *)d_rec.p, (const T *)d_rp_rec.p);
+        hipLaunchKernelGGL((k_pcg_forest_edges<T>), dim3(fo.nodes), dim3(256), 0, st, forest_dev(), (const T *)d_rec.p, (const T *)rp.rec.p);
     }
     void launch_forest_factor()
     {
         with_flag(fo.width == 9, [&](auto W9) {
-            hipLaunchKernelGGL((k_pcg_forest_factor<T, W9() ? 9 : 6>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)d_rp_rec.p);
+            hipLaunchKernelGGL((k_pcg_forest_factor<T, W9() ? 9 : 6>), dim3(fo.ntrees), dim3(64), 0, st, forest_dev(), (const T *)d_pcg_M.p, (const T *)rp.rec.p);
         });
     }
     template <bool START> void launch_forest_apply(double *part)
@@ -1031,9 +1140,9 @@ template <typename T> struct Solver final : SolverBase {
         if (max_tree == 0) max_tree = kind == BA_PRECOND_VISIBILITY_FOREST ? BA_PCG_VIS_MAX_TREE_DEFAULT : BA_PCG_MAX_TREE_DEFAULT;
         Forest nf;
         int rc;
-        if ((rc = build_forest(h_rp_pair, kind, max_tree, nf))) return rc;
+        if ((rc = build_forest(rp.h_pair, kind, max_tree, nf))) return rc;
         HIPCHK(hipStreamSynchronize(st));
-        fo.swap(nf);
+        fo = std::move(nf);
         precond_kind = kind; precond_max_tree = max_tree;
         drop_trial_graphs(); // (captured with the old launch sequence)
         return BA_OK;
@@ -1066,13 +1175,6 @@ template <typename T> struct Solver final : SolverBase {
         DevBuf<int> members, wide;   // [ngrouped]; [nwide]: the slots of groups of more than BA_SHARE_LOCAL chunks
         DevBuf<double> part;         // [nslots][3]
         std::vector<int> h_gptr, h_members; // host copy: the refusals of set_state / set_constant
-        void swap(Share &o)
-        {
-            std::swap(ngroups, o.ngroups); std::swap(ngrouped, o.ngrouped); std::swap(largest, o.largest); std::swap(nchunks, o.nchunks);
-            std::swap(nslots, o.nslots); std::swap(nwide, o.nwide);
-            desc.swap(o.desc); members.swap(o.members); wide.swap(o.wide); part.swap(o.part);
-            h_gptr.swap(o.h_gptr); h_members.swap(o.h_members);
-        }
         size_t bytes() const { return bytes_of(desc) + bytes_of(members) + bytes_of(wide) + bytes_of(part); }
     } sh;
     bool share_on() const { return sh.ngroups > 0; }
@@ -1127,9 +1229,9 @@ template <typename T> struct Solver final : SolverBase {
                 std::vector<T> hc;
                 if ((rc = dl(d_cam[0].p, 15 * (size_t)N, hc))) return rc;
                 if (!share_equal(gptr, members, hc.data(), N)) return BA_ERR_ARG;
-                if (masked && d_cmask.p) {
+                if (mk.on && mk.cmask.p) {
                     std::vector<unsigned short> hm((size_t)N);
-                    HIPCHK(hipMemcpy(hm.data(), d_cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(hm.data(), mk.cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
                     if (!share_mask_uniform(gptr, members, hm.data())) return BA_ERR_ARG;
                 }
                 ba_share_plan pl;
@@ -1143,9 +1245,9 @@ template <typename T> struct Solver final : SolverBase {
             }
         }
         HIPCHK(hipStreamSynchronize(st));
-        sh.swap(ns);
+        sh = std::move(ns);
         drop_trial_graphs(); // (captured with the old launch sequence)
-        have_step = false; // (xTest is the step of the other group set: its members' f, k1, k2 need not be equal)
+        vf.step_dropped(); // (xTest is the step of the other group set: its members' f, k1, k2 need not be equal)
         return BA_OK;
     }
     int shared_info(long long *out4) override
@@ -1311,7 +1413,7 @@ template <typename T> struct Solver final : SolverBase {
         if (dmin == 0) dmin = BA_DAMP_DIAG_MIN_DEFAULT;
         if (dmax == 0) dmax = BA_DAMP_DIAG_MAX_DEFAULT;
         const T tmin_ = (T)dmin, tmax_ = (T)dmax; // (the kernels see them in the solver's scalar type)
-        if (!(tmin_ > 0) || !(tmin_ <= tmax_) || !std::isfinite((double)tmin_) || !std::isfinite((double)tmax_)) return BA_ERR_ARG;
+        if (!positive_in_T(dmin) || !positive_in_T(dmax) || !(tmin_ <= tmax_)) return BA_ERR_ARG;
         drop_trial_graphs(); // (captured with the other instantiations or other bounds)
         damp_kind = k; damp_min = (double)tmin_; damp_max = (double)tmax_;
         return BA_OK;
@@ -1344,7 +1446,6 @@ template <typename T> struct Solver final : SolverBase {
         }
         return BA_OK;
     }
-    template <typename B> static size_t bytes_of(const B &b) { return b.p ? sizeof(*b.p) * b.n : 0; }
     size_t device_bytes() const override
     {
         size_t n = 0;
@@ -1357,22 +1458,17 @@ template <typename T> struct Solver final : SolverBase {
                               &d_q1lam, &d_mQl, &d_mQR, &d_R22, &d_qB, &d_qAcopy, &d_dbgr, &d_dbg2, &d_stage, &d_pcg_M, &d_pcg_b, &d_pcg_r,
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
-        return n + bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg_part_s) + bytes_of(d_pcg) + bytes_of(d_cmask) +
-               bytes_of(d_pfix) + bytes_of(d_cov) + bytes_of(d_cov_flag) + mc_bytes() + bytes_of(d_wobs) + bytes_of(d_dl_keep) + bytes_of(d_dl_part) + tri_bytes() + prior_bytes() + relpose_bytes() + fo.bytes() + sh.bytes();
+        n += bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg_part_s) + bytes_of(d_pcg) + mc_bytes();
+        return n + mk.bytes() + md.bytes() + pr.bytes() + rp.bytes() + dg.bytes() + tr.bytes() + cv.bytes() + fo.bytes() + sh.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
-    // The work buffer is the solver's only state of this feature: [C: cov_ld x (Dp + 64) | one panel Y: cov_ld x NB | the blocks'
+    // The work buffer cv.buf is the solver's only state of this feature: [C: cov_ld x (Dp + 64) | one panel Y: cov_ld x NB | the blocks'
     // inverses W | the pivots (Dp) | the scaling (Dp) | the last trial's dx_c while the assembly borrows its buffer], allocated by the first compute.  The LM trial's own S, Wp, Winv and flags are not
     // used by the factorisation here (S is assembled as a trial assembles it and then only read), x, xTest, J and the mask not at all.
-    DevBuf<T> d_cov;
-    DevBuf<int> d_cov_flag;
-    bool cov_valid = false; // a result that BA_GET-style reads may return: cleared by linearize / accept / set_state / set_constant / minimize
-    bool have_lin = false;  // a linearisation at x exists
-    double cov_lambda = 0, cov_ms[4] = {0, 0, 0, 0};
     int cov_ld() const { return ((Dp + D + NAUG + NB - 1) / NB) * NB + 64; }
     size_t cov_nmat() const { return (size_t)cov_ld() * (Dp + 64); }
-    T *cov_wp() const { return d_cov.p + cov_nmat(); }
+    T *cov_wp() const { return cv.buf.p + cov_nmat(); }
     T *cov_winv() const { return cov_wp() + (size_t)cov_ld() * NB; }
     T *cov_dv() const { return cov_winv() + (size_t)((D + NB - 1) / NB) * NB * NB; }
     T *cov_sc() const { return cov_dv() + Dp; }
@@ -1384,16 +1480,16 @@ template <typename T> struct Solver final : SolverBase {
     void launch_cov_eliminate(int *flag)
     {
         launch_eliminate();
-        if (masked && d_pfix.p)
+        if (mk.on && mk.pfix.p)
             hipLaunchKernelGGL((k_cov_fixed_records<T>), dim3((std::max(Kl, Ml) + 255) / 256), dim3(256), 0, st, Kl, Ml, (int)BA_REC, (const int *)d_obs_pt.p,
-                               (const unsigned char *)d_pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
+                               (const unsigned char *)mk.pfix.p, d_rec.p, d_dinv.p, d_tvec.p, d_tri.p);
         if (Ml <= 0) return;
         if (priors()) // (a point prior is in U0 and in no observation's Jp)
-            hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)d_pfix.p,
+            hipLaunchKernelGGL((k_cov_points_check_u0<T>), dim3(gM), dim3(256), 0, st, Ml, (const T *)d_U0.p, (const unsigned char *)mk.pfix.p,
                                (const T *)(d_scal.p + SC_LAMBDA), flag);
         else
             hipLaunchKernelGGL((k_cov_points_check<T>), dim3(gM), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, (const T *)d_Jp.p,
-                               (const unsigned char *)d_pfix.p, (const T *)(d_scal.p + SC_LAMBDA), flag);
+                               (const unsigned char *)mk.pfix.p, (const T *)(d_scal.p + SC_LAMBDA), flag);
     }
     // a request for blocks: counts, null pointers, index ranges (single shard: the shard's points are the problem's)
     bool cov_request_ok(int n_pairs, const int *cam_pairs, const double *cam_cov, int n_pts, const int *pt_ids, const double *pt_cov) const
@@ -1411,52 +1507,50 @@ template <typename T> struct Solver final : SolverBase {
         if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG; // (a single-precision inverse at these condition numbers is noise)
         else {
             // refusals: host side, before any launch
-            if ((kind != BA_CHOLESKY && kind != BA_QRCHOL) || sharded() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda))
+            if ((kind != BA_CHOLESKY && kind != BA_QRCHOL) || sharded() || !vf.have_lin || vf.mask_pending || !(lambda >= 0) || !std::isfinite(lambda))
                 return BA_ERR_ARG;
             const DampOff identity(damp_off); // (this call's lambda means J'J + lambda I whatever ba_solver_set_damping holds)
-            cov_valid = false;
+            vf.cov_dropped();
             int rc;
-            if (!d_cov.p) {
-                if ((rc = d_cov.alloc(cov_count())) || (rc = d_cov_flag.alloc(1))) {
-                    (void)hipGetLastError(); // (the solver stays usable)
-                    d_cov.release(); d_cov_flag.release();
-                    return rc;
-                }
+            if (!cv.buf.p) {
+                Cov nc;
+                if ((rc = nc.buf.alloc(cov_count())) || (rc = nc.flag.alloc(1))) { (void)hipGetLastError(); return rc; } // (the solver stays usable)
+                cv = std::move(nc);
             }
             const int ldc = cov_ld();
             int flag = 0;
-            HIPCHK(hipMemsetAsync(d_cov_flag.p, 0, sizeof(int), st));
+            HIPCHK(hipMemsetAsync(cv.flag.p, 0, sizeof(int), st));
             if ((rc = set_lambda((T)lambda))) return rc;
             HIPCHK(hipEventRecord(ev[EV_T0], st));
             // S(lambda) as a trial assembles it (segment A + the diagonal's lambda), left unfactored in d_S.  The assembly arms the back
             // sweep's hand-over vector, which is where the last trial's dx_c lives (BA_GET_DX): kept aside and put back.
             HIPCHK(hipMemcpyAsync(cov_dxsave(), d_dxc.p, sizeof(T) * d_dxc.n, hipMemcpyDeviceToDevice, st));
-            launch_cov_eliminate(d_cov_flag.p);
+            launch_cov_eliminate(cv.flag.p);
             launch_schur();
             launch_post_reduce();
             HIPCHK(hipMemcpyAsync(d_dxc.p, cov_dxsave(), sizeof(T) * d_dxc.n, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipMemsetAsync(d_cov.p, 0, sizeof(T) * cov_nmat(), st));
-            hipLaunchKernelGGL((k_cov_scale<T>), dim3((D + 255) / 256), dim3(256), 0, st, D, ld, (const T *)d_S.p, (const unsigned short *)d_cmask.p,
-                               cov_sc(), d_cov_flag.p);
-            hipLaunchKernelGGL((k_cov_stage<T>), dim3(((D + NB - 1) / NB) * NB), dim3(256), 0, st, D, Dp, ld, (const T *)d_S.p, (const T *)cov_sc(), ldc, d_cov.p);
+            HIPCHK(hipMemsetAsync(cv.buf.p, 0, sizeof(T) * cov_nmat(), st));
+            hipLaunchKernelGGL((k_cov_scale<T>), dim3((D + 255) / 256), dim3(256), 0, st, D, ld, (const T *)d_S.p, (const unsigned short *)mk.cmask.p,
+                               cov_sc(), cv.flag.p);
+            hipLaunchKernelGGL((k_cov_stage<T>), dim3(((D + NB - 1) / NB) * NB), dim3(256), 0, st, D, Dp, ld, (const T *)d_S.p, (const T *)cov_sc(), ldc, cv.buf.p);
             HIPCHK(hipEventRecord(ev[EV_T1], st));
-            HIPCHK(hipMemcpyAsync(&flag, d_cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&flag, cv.flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (flag) return BA_ERR_SINGULAR; // a free parameter nobody observes: nothing is factored
             // launch-per-step factorisation (no workgroup waits for another one) with the stacked rows riding along
-            ba_ldlt_factor<T, NB>(st, Dp + D, ((D + NB - 1) / NB) * NB /* the last block column padded with unit pivots */, ldc, d_cov.p, cov_wp(), cov_winv(), (int *)nullptr, 0, (T *)nullptr, /*safe*/ true, 0);
+            ba_ldlt_factor<T, NB>(st, Dp + D, ((D + NB - 1) / NB) * NB /* the last block column padded with unit pivots */, ldc, cv.buf.p, cov_wp(), cov_winv(), (int *)nullptr, 0, (T *)nullptr, /*safe*/ true, 0);
             HIPCHK(hipEventRecord(ev[EV_T2], st));
-            hipLaunchKernelGGL((k_cov_diag<T>), dim3((Dp + 255) / 256), dim3(256), 0, st, D, Dp, ldc, (const T *)d_cov.p, (const T *)cov_sc(), cov_dv(), d_cov_flag.p);
+            hipLaunchKernelGGL((k_cov_diag<T>), dim3((Dp + 255) / 256), dim3(256), 0, st, D, Dp, ldc, (const T *)cv.buf.p, (const T *)cov_sc(), cov_dv(), cv.flag.p);
             const int nt = (D + 63) / 64;
-            hipLaunchKernelGGL((k_cov_syrk<T>), dim3(nt * (nt + 1) / 2), dim3(256), 0, st, D, Dp, ldc, d_cov.p, (const T *)cov_dv());
+            hipLaunchKernelGGL((k_cov_syrk<T>), dim3(nt * (nt + 1) / 2), dim3(256), 0, st, D, Dp, ldc, cv.buf.p, (const T *)cov_dv());
             HIPCHK(hipEventRecord(ev[EV_T3], st));
-            HIPCHK(hipMemcpyAsync(&flag, d_cov_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&flag, cv.flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             HIPCHK(hipGetLastError());
-            cov_ms[0] = ev_ms(EV_T0, EV_T1); cov_ms[1] = ev_ms(EV_T1, EV_T2); cov_ms[2] = ev_ms(EV_T2, EV_T3);
+            cv.ms[0] = ev_ms(EV_T0, EV_T1); cv.ms[1] = ev_ms(EV_T1, EV_T2); cv.ms[2] = ev_ms(EV_T2, EV_T3);
             if (flag) return BA_ERR_SINGULAR; // a pivot <= 0 (or not finite): no result is left behind
-            cov_lambda = lambda;
-            cov_valid = true;
+            cv.lambda = lambda;
+            vf.cov_computed();
             return BA_OK;
         }
     }
@@ -1465,7 +1559,7 @@ template <typename T> struct Solver final : SolverBase {
     {
         if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG;
         else {
-            if (!cov_valid || !cov_request_ok(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov)) return BA_ERR_ARG;
+            if (!vf.cov_valid || !cov_request_ok(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov)) return BA_ERR_ARG;
             const int ldc = cov_ld();
             int rc;
             HIPCHK(hipStreamSynchronize(st));
@@ -1475,7 +1569,7 @@ template <typename T> struct Solver final : SolverBase {
                 if ((rc = d_idx.alloc((size_t)2 * n_pairs)) || (rc = d_out.alloc((size_t)81 * n_pairs))) { (void)hipGetLastError(); return rc; }
                 HIPCHK(hipMemcpy(d_idx.p, cam_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
                 hipLaunchKernelGGL((k_cov_get_cams<T>), dim3((unsigned)(((size_t)81 * n_pairs + 255) / 256)), dim3(256), 0, st, n_pairs, (const int *)d_idx.p, ldc,
-                                   (const T *)d_cov.p, (const unsigned short *)d_cmask.p, d_out.p);
+                                   (const T *)cv.buf.p, (const unsigned short *)mk.cmask.p, d_out.p);
                 HIPCHK(hipStreamSynchronize(st));
                 HIPCHK(hipMemcpy(cam_cov, d_out.p, sizeof(double) * 81 * (size_t)n_pairs, hipMemcpyDeviceToHost));
             }
@@ -1488,19 +1582,19 @@ template <typename T> struct Solver final : SolverBase {
                 HIPCHK(hipEventRecord(ev[EV_T4], st));
                 if (priors()) // (CHOLESKY: the only kind with both)
                     hipLaunchKernelGGL((k_cov_points_u0<T, true>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
-                                       (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
-                                       (const T *)d_cov.p, d_out.p, (const T *)d_U0.p, Ml);
+                                       (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)mk.pfix.p, (T)cv.lambda, ldc,
+                                       (const T *)cv.buf.p, d_out.p, (const T *)d_U0.p, Ml);
                 else if (chol_elim())
                     hipLaunchKernelGGL((k_cov_points<T, true>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
-                                       (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
-                                       (const T *)d_cov.p, d_out.p);
+                                       (const int *)d_obs_cam.p, (const T *)d_JcA.p, (const T *)d_Jp.p, (const unsigned char *)mk.pfix.p, (T)cv.lambda, ldc,
+                                       (const T *)cv.buf.p, d_out.p);
                 else
                     hipLaunchKernelGGL((k_cov_points<T, false>), dim3(n_pts), dim3(64), 0, st, n_pts, (const int *)d_idx.p, Kl, (const int *)d_pt_ptr.p,
-                                       (const int *)d_obs_cam.p, (const T *)d_Jc.p, (const T *)d_Jp.p, (const unsigned char *)d_pfix.p, (T)cov_lambda, ldc,
-                                       (const T *)d_cov.p, d_out.p);
+                                       (const int *)d_obs_cam.p, (const T *)d_Jc.p, (const T *)d_Jp.p, (const unsigned char *)mk.pfix.p, (T)cv.lambda, ldc,
+                                       (const T *)cv.buf.p, d_out.p);
                 HIPCHK(hipEventRecord(ev[EV_T5], st));
                 HIPCHK(hipStreamSynchronize(st));
-                cov_ms[3] = ev_ms(EV_T4, EV_T5);
+                cv.ms[3] = ev_ms(EV_T4, EV_T5);
                 HIPCHK(hipMemcpy(pt_cov, d_out.p, sizeof(double) * 9 * (size_t)n_pts, hipMemcpyDeviceToHost));
             }
             HIPCHK(hipGetLastError());
@@ -1511,7 +1605,7 @@ template <typename T> struct Solver final : SolverBase {
     // with points: the point kernel
     int cov_timing(double *ms4) override
     {
-        for (int q = 0; q < 4; q++) ms4[q] = cov_ms[q];
+        for (int q = 0; q < 4; q++) ms4[q] = cv.ms[q];
         return BA_OK;
     }
 
@@ -1550,7 +1644,7 @@ template <typename T> struct Solver final : SolverBase {
         }
         double *v = d_mc_vec.p, *pt = d_mc_part.p;
         c = McRun{v, v + DV, v + 2 * DV, v + 3 * DV, v + 4 * DV, v + 5 * DV, pt, pt + (size_t)gm * BA_MC_NR, pt + 2 * (size_t)gm * BA_MC_NR, gm, max_iter,
-                  rel_tol * rel_tol, masked ? (const unsigned short *)d_cmask.p : nullptr, masked ? (const unsigned char *)d_pfix.p : nullptr,
+                  rel_tol * rel_tol, mk.on ? (const unsigned short *)mk.cmask.p : nullptr, mk.on ? (const unsigned char *)mk.pfix.p : nullptr,
                   ba_cov_pcg_stats{}};
         return BA_OK;
     }
@@ -1655,7 +1749,7 @@ template <typename T> struct Solver final : SolverBase {
         if constexpr (!std::is_same<T, double>::value) return BA_ERR_ARG;
         else {
             // refusals: host side, before any launch
-            if (!iterative() || sharded() || share_on() || !have_lin || mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
+            if (!iterative() || sharded() || share_on() || !vf.have_lin || vf.mask_pending || !(lambda >= 0) || !std::isfinite(lambda) || max_iter < 0 ||
                 !(rel_tol >= 0 && rel_tol < 1) || !cov_request_ok(n_pairs, cam_pairs, cam_cov, n_pts, pt_ids, pt_cov))
                 return BA_ERR_ARG;
             const DampOff identity(damp_off); // (this call's lambda means J'J + lambda I whatever ba_solver_set_damping holds)
@@ -1666,8 +1760,8 @@ template <typename T> struct Solver final : SolverBase {
             std::vector<unsigned short> hcm((size_t)N, 0);
             std::vector<unsigned char> hpf((size_t)(Ml > 0 ? Ml : 1), 0);
             HIPCHK(hipStreamSynchronize(st));
-            if (masked && d_cmask.p) HIPCHK(hipMemcpy(hcm.data(), d_cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
-            if (masked && d_pfix.p && Ml > 0) HIPCHK(hipMemcpy(hpf.data(), d_pfix.p, (size_t)Ml, hipMemcpyDeviceToHost));
+            if (mk.on && mk.cmask.p) HIPCHK(hipMemcpy(hcm.data(), mk.cmask.p, sizeof(unsigned short) * (size_t)N, hipMemcpyDeviceToHost));
+            if (mk.on && mk.pfix.p && Ml > 0) HIPCHK(hipMemcpy(hpf.data(), mk.pfix.p, (size_t)Ml, hipMemcpyDeviceToHost));
             DevBuf<int> d_req; // pairs [2 n_pairs] | order [n_pairs] | point batch: ids [3], slots [3]
             DevBuf<double> d_out;
             if ((rc = d_req.alloc((size_t)3 * n_pairs + 6)) || (rc = d_out.alloc((size_t)81 * n_pairs + (size_t)9 * n_pts + 1))) { (void)hipGetLastError(); return rc; }
@@ -1740,26 +1834,21 @@ template <typename T> struct Solver final : SolverBase {
         if (Ml > 0) { // the camera retraction rides as one more block at the end of the grid
             const ba_cam_retract_args cr{N, d_cam[0].p, d_dxc.p, d_gcg.p, d_cam[1].p, d_scal.p, (int)SC_RHO_C};
             // masked: the first reader of dx_c behind every kind's reduced solve forces the fixed rows (and fixed points) to a zero step
-            with_flags(masked, marq(), [&](auto MASKED, auto MARQ) {
+            with_flags(mk.on, marq(), [&](auto MASKED, auto MARQ) {
                 hipLaunchKernelGGL((k_backsub<T, 8, MASKED(), MARQ()>), dim3(gB + 1), dim3(256), 0, st, Ml, d_pt_ptr.p, d_obs_cam.p, d_rec.p, d_dinv.p,
                                    d_tvec.p, d_tri.p, d_dxc.p, d_gp.p, d_pts[0].p, d_scal.p + SC_LAMBDA, d_dxp.p, d_pts[1].p, d_part_bs.p, d_pperm.p, gB, cr,
-                                   ba_fix_args{d_cmask.p, d_pfix.p}, damp_diag());
+                                   ba_fix_args{mk.cmask.p, mk.pfix.p}, damp_diag());
             });
         } else // (an empty shard keeps the zero partial sums written at creation)
-            with_flags(masked, marq(), [&](auto MASKED, auto MARQ) {
+            with_flags(mk.on, marq(), [&](auto MASKED, auto MARQ) {
                 hipLaunchKernelGGL((k_retract_cams<T, MASKED(), MARQ()>), dim3(1), dim3(256), 0, st, N, d_cam[0].p, d_dxc.p, d_gcg.p, d_scal.p + SC_LAMBDA,
-                                   d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)d_cmask.p, damp_diag());
+                                   d_cam[1].p, d_scal.p, (int)SC_RHO_C, (const unsigned short *)mk.cmask.p, damp_diag());
             });
     }
 
     // ---- parameters held constant (ba_solver_set_constant) ---------------------------------------------------------------------------
     // A mask with a bit set selects the masked instantiations of k_eval, k_backsub and k_retract_cams; nothing else changes (S, the
     // records, J2bot and the reduced solves see zero columns).  No mask: no buffers, the kernels of a solver that never had one.
-    DevBuf<unsigned short> d_cmask; // [N]
-    DevBuf<unsigned char> d_pfix;   // [Ml] of this shard
-    bool masked = false;
-    bool mask_pending = false; // a mask or a measurement model set, or points re-seated by triangulate(), since the last linearisation: J is
-                               // the old one's, try_step refuses
     int set_constant(const unsigned short *cm, const unsigned char *pf) override
     {
         bool any = false, all = sx.M > 0 || N > 0;
@@ -1779,20 +1868,18 @@ template <typename T> struct Solver final : SolverBase {
         if (any && all) return BA_ERR_ARG; // nothing left to optimise
         if (share_on() && !share_mask_uniform(sh.h_gptr, sh.h_members, cm)) return BA_ERR_ARG; // (a shared parameter is fixed for all or for none)
         HIPCHK(hipStreamSynchronize(st));
-        cov_valid = false; // (here already: ba_solver_covariance_get reads d_cmask, which an allocation that fails below leaves half set)
-        if (!any) { d_cmask.release(); d_pfix.release(); }
-        else {
+        vf.cov_dropped(); // (in front of everything that can fail, as ever: ba_solver_covariance_get reads the mask)
+        Mask nm;
+        if (any) {
             int rc;
             std::vector<unsigned short> hc((size_t)N, 0);
             std::vector<unsigned char> hp((size_t)(Ml > 0 ? Ml : 1), 0);
             for (int a = 0; cm && a < N; a++) hc[a] = cm[a];
             for (int j = 0; pf && j < Ml; j++) hp[j] = pf[sx.p0 + j] != 0;
-            if (!d_cmask.p && (rc = d_cmask.alloc(hc.size()))) return rc;
-            if (!d_pfix.p && (rc = d_pfix.alloc(hp.size()))) return rc;
-            HIPCHK(hipMemcpy(d_cmask.p, hc.data(), sizeof(unsigned short) * hc.size(), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_pfix.p, hp.data(), hp.size(), hipMemcpyHostToDevice));
+            if ((rc = nm.cmask.upload(hc)) || (rc = nm.pfix.upload(hp))) { (void)hipGetLastError(); return rc; }
+            nm.on = true;
         }
-        masked = any;
+        mk = std::move(nm);
         return model_changed();
     }
 
@@ -1800,79 +1887,56 @@ template <typename T> struct Solver final : SolverBase {
     // Anything but the reference's psi at its 0.5 px without weights selects the MODEL instantiations of k_eval; nothing else changes
     // (everything downstream is built from e and J).  psi at another tau goes there too: the default kernels keep the reference's
     // clamps 1 / max(1e-15, .), which falsify dE/dr below |r|^2 = 1e-15, and the model's contract is a derivative that is right down to 0.  `tau` stays the reference's threshold: ba_solver_stats is its only other consumer.
-    int loss_kind = BA_LOSS_REFERENCE;
-    T loss_scale = (T)0.5;
-    DevBuf<T> d_wobs; // [Kl] of this shard, the solver's observation order (like d_meas)
-    bool model() const { return loss_kind != BA_LOSS_REFERENCE || loss_scale != (T)0.5 || d_wobs.p != nullptr; }
+    bool model() const { return md.loss_kind != BA_LOSS_REFERENCE || md.loss_scale != (T)0.5 || md.wobs.p != nullptr; }
     // the end of every setter that changes what a linearisation computes (mask, model, priors, constraints): the captured iterations
     // hold the other instantiations, kernel arguments and buffer addresses and are captured again on the next ba_minimize
-    int model_changed()
-    {
-        cov_valid = false;
-        dl_valid = false;
-        drop_trial_graphs();
-        mask_pending = true;
-        have_step = false;
-        return BA_OK;
-    }
+    // (measurement: the loss or the weights, which triangulate() must not meet before a linearisation has taken them up)
+    int model_changed(bool measurement = false) { drop_trial_graphs(); vf.model_changed(measurement); return BA_OK; }
     int set_loss(int kind, double scale) override
     {
         if (kind < BA_LOSS_REFERENCE || kind > BA_LOSS_CAUCHY) return BA_ERR_ARG;
         if (kind == BA_LOSS_TRIVIAL) scale = 1.0; // (ignored)
-        else if (!(scale > 0) || !std::isfinite(scale) || !((T)scale > 0) || !std::isfinite((T)scale)) return BA_ERR_ARG;
+        else if (!positive_in_T(scale)) return BA_ERR_ARG;
         HIPCHK(hipStreamSynchronize(st));
-        loss_kind = kind;
-        loss_scale = (T)scale;
-        model_pending = true;
-        return model_changed();
+        md.loss_kind = kind; md.loss_scale = (T)scale;
+        return model_changed(true);
     }
     int set_obs_weights(const double *w) override
     {
         for (int i = 0; w && i < sx.K; i++)
-            if (!(w[i] > 0) || !std::isfinite(w[i]) || !((T)w[i] > 0) || !std::isfinite((T)w[i])) return BA_ERR_ARG;
+            if (!positive_in_T(w[i])) return BA_ERR_ARG;
         HIPCHK(hipStreamSynchronize(st));
-        if (!w) d_wobs.release();
-        else {
+        DevBuf<T> nw;
+        if (w) {
             std::vector<T> hw((size_t)(Kl > 0 ? Kl : 1), (T)1.0);
             for (int i = 0; i < Kl; i++) hw[i] = (T)w[sx.perm[sx.o0 + i]];
             int rc;
-            if (!d_wobs.p && (rc = d_wobs.alloc(hw.size()))) return rc;
-            HIPCHK(hipMemcpy(d_wobs.p, hw.data(), sizeof(T) * hw.size(), hipMemcpyHostToDevice));
+            if ((rc = nw.upload(hw))) { (void)hipGetLastError(); return rc; }
         }
-        model_pending = true;
-        return model_changed();
+        md.wobs = std::move(nw);
+        return model_changed(true);
     }
 
     // ---- Gaussian priors (ba_solver_set_point_priors / _centre_priors / _intrinsics_priors; ba_prior.hip.h) ------
-    // Compact device lists per type; the block partials of k_prior live behind k_eval's in d_part_e (energies, 3 gP) and behind
-    // k_point_prep's in d_part_pm (point diagonals, gP), so that the existing second-stage jobs sum them in their fixed order.  No prior:
-    // no list, gP = 0, the buffers at their old sizes and not one launch or argument more.
-    DevBuf<int> d_pr_id[3], d_pr_lonely; // d_pr_lonely: the points with a prior and no observation (k_prior_lonely)
-    DevBuf<T> d_pr_x0[3], d_pr_info[3], d_part_pr; // d_part_pr: [3][gP] prior energies of the last linearisation
-    int n_pr[3] = {0, 0, 0};
-    int gP = 0;
-    bool priors() const { return gP > 0; }
+    // Compact device lists per type; the block partials of k_prior live behind k_eval's in d_part_e (energies) and behind
+    // k_point_prep's in d_part_pm (point diagonals), so that the existing second-stage jobs sum them in their fixed order.  No prior:
+    // no list, pr.g = 0, the buffers at their old sizes and not one launch or argument more.
+    bool priors() const { return pr.g > 0; }
     // The fused linearisation eliminates the next trial's points from registers, before a prior could join U0: with priors its records
     // are not used -- every trial runs k_elim_chol on the U0 / gp that k_prior has completed -- while J, U0, gp and the energy partials
     // still come from the kernel a solver without priors runs (so priors without information leave its bits alone, fp32 included,
     // where the separate-launch linearisation does not reproduce the fused one's bits).
     bool fused_records() const { return fuse && !priors() && !marq(); } // (Marquardt: the records of a lambda I elimination are not the trial's)
-    size_t prior_bytes() const
-    {
-        size_t n = bytes_of(d_part_pr) + bytes_of(d_pr_lonely);
-        for (int q = 0; q < 3; q++) n += bytes_of(d_pr_id[q]) + bytes_of(d_pr_x0[q]) + bytes_of(d_pr_info[q]);
-        return n;
-    }
     // lin: the linearisation part (adds into U0 / gp / V / gc of the state `which`); else the energy at xTest alone
     void launch_prior(bool lin, int which, const int *go)
     {
-        ba_prior_args<T> pa{n_pr[0], n_pr[1], n_pr[2], d_pr_id[0].p, d_pr_id[1].p, d_pr_id[2].p, d_pr_x0[0].p, d_pr_info[0].p,
-                            d_pr_x0[1].p, d_pr_info[1].p, d_pr_x0[2].p, d_pr_info[2].p};
+        ba_prior_args<T> pa{pr.of[0].n, pr.of[1].n, pr.of[2].n, pr.of[0].id.p, pr.of[1].id.p, pr.of[2].id.p, pr.of[0].x0.p, pr.of[0].info.p,
+                            pr.of[1].x0.p, pr.of[1].info.p, pr.of[2].x0.p, pr.of[2].info.p};
         // (the mask is a property of the linearisation: the energy at xTest always runs the unmasked instantiation, MASK = LIN && ...)
-        with_flags(lin, masked, [&](auto LIN, auto MASKED) {
-            hipLaunchKernelGGL((k_prior<T, LIN(), LIN() && MASKED()>), dim3(gP), dim3(256), 0, st, pa, N, Ml, (const T *)d_cam[which].p,
-                               (const T *)d_pts[which].p, d_U0.p, d_gp.p, d_V.p, d_gc.p, d_part_e.p + gE, d_part_pr.p, d_part_pm.p + gM, go,
-                               (const unsigned short *)d_cmask.p, (const unsigned char *)d_pfix.p);
+        with_flags(lin, mk.on, [&](auto LIN, auto MASKED) {
+            hipLaunchKernelGGL((k_prior<T, LIN(), LIN() && MASKED()>), dim3(pr.g), dim3(256), 0, st, pa, N, Ml, (const T *)d_cam[which].p,
+                               (const T *)d_pts[which].p, d_U0.p, d_gp.p, d_V.p, d_gc.p, part_e_priors(), pr.part.p, part_pm_priors(), go,
+                               (const unsigned short *)mk.cmask.p, (const unsigned char *)mk.pfix.p);
         });
     }
     // type 0 points (info = L, 9 per prior), 1 centres (L), 2 intrinsics (info = w, 3 per prior)
@@ -1880,26 +1944,14 @@ template <typename T> struct Solver final : SolverBase {
     {
         if (!chol_elim() || sharded() || n < 0 || (n > 0 && (!ids || !x0 || !info))) return BA_ERR_ARG;
         const int lim = type == 0 ? sx.M : N, ni = type == 2 ? 3 : 9;
-        if (n > lim) return BA_ERR_ARG; // (some index is listed twice)
-        {
-            std::vector<char> seen((size_t)(lim > 0 ? lim : 1), 0);
-            for (int q = 0; q < n; q++) {
-                if (ids[q] < 0 || ids[q] >= lim || seen[ids[q]]) return BA_ERR_ARG;
-                seen[ids[q]] = 1;
-            }
-        }
-        for (size_t q = 0; q < (size_t)3 * n; q++)
-            if (!std::isfinite(x0[q]) || !std::isfinite((T)x0[q])) return BA_ERR_ARG;
-        for (size_t q = 0; q < (size_t)ni * n; q++)
-            if (!std::isfinite(info[q]) || !std::isfinite((T)info[q])) return BA_ERR_ARG;
+        if (!distinct_ids(n, ids, lim) || !finite_in_T(x0, (size_t)3 * n) || !finite_in_T(info, (size_t)ni * n)) return BA_ERR_ARG;
         HIPCHK(hipStreamSynchronize(st));
-        int cnt[3] = {n_pr[0], n_pr[1], n_pr[2]};
-        cnt[type] = n;
-        const int tot = cnt[0] + cnt[1] + cnt[2], gp_new = (tot + 255) / 256;
+        const int tot = pr.of[0].n + pr.of[1].n + pr.of[2].n - pr.of[type].n + n, gp_new = (tot + 255) / 256;
         int rc;
         // everything that can fail first: the solver is unchanged behind an error
-        DevBuf<int> nid, nlone;
-        DevBuf<T> nx0, ninfo, npe, npm, npr;
+        PriorList nl;
+        DevBuf<int> nlone;
+        DevBuf<T> npart;
         if (type == 0) {
             std::vector<int> lone;
             for (int q = 0; q < n; q++)
@@ -1911,26 +1963,24 @@ template <typename T> struct Solver final : SolverBase {
             std::vector<T> hx((size_t)3 * n), hi((size_t)ni * n);
             for (size_t q = 0; q < hx.size(); q++) hx[q] = (T)x0[q];
             for (size_t q = 0; q < hi.size(); q++) hi[q] = (T)info[q];
-            if ((rc = nid.upload(hid)) || (rc = nx0.upload(hx)) || (rc = ninfo.upload(hi))) { (void)hipGetLastError(); return rc; }
+            if ((rc = nl.id.upload(hid)) || (rc = nl.x0.upload(hx)) || (rc = nl.info.upload(hi))) { (void)hipGetLastError(); return rc; }
+            nl.n = n;
         }
-        if (gp_new != gP) {
-            if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gp_new + 2 * (size_t)gR)) || (rc = npm.alloc((size_t)gM + gp_new)) ||
-                (rc = npr.alloc(3 * (size_t)gp_new))) { (void)hipGetLastError(); return rc; }
-            HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
-            HIPCHK(hipMemset(npm.p, 0, sizeof(T) * npm.n));
-            if (npr.p) HIPCHK(hipMemset(npr.p, 0, sizeof(T) * npr.n));
-            d_part_e.swap(npe); d_part_pm.swap(npm); d_part_pr.swap(npr);
-            gP = gp_new;
+        if (gp_new != pr.g) {
+            if ((rc = npart.alloc(3 * (size_t)gp_new))) { (void)hipGetLastError(); return rc; }
+            if (npart.p) HIPCHK(hipMemset(npart.p, 0, sizeof(T) * npart.n));
+            if ((rc = resize_partials(gp_new, rp.g))) return rc;
+            pr.part = std::move(npart);
+            pr.g = gp_new;
         }
-        d_pr_id[type].swap(nid); d_pr_x0[type].swap(nx0); d_pr_info[type].swap(ninfo);
-        if (type == 0) d_pr_lonely.swap(nlone);
-        n_pr[type] = n;
-        return model_changed(); // (the old buffers leave with the locals)
+        pr.of[type] = std::move(nl); // (one type's lists are what a call replaces: the other two stay)
+        if (type == 0) pr.lonely = std::move(nlone);
+        return model_changed();
     }
     // the energies a linearisation kept aside: q rows of g block partials, each summed in index order in T (zeros for g = 0)
     int kept_energy(const T *part, int q, int g, double *out)
     {
-        if (!chol_elim() || sharded() || !have_lin || mask_pending) return BA_ERR_ARG;
+        if (!chol_elim() || sharded() || !vf.have_lin || vf.mask_pending) return BA_ERR_ARG;
         std::vector<T> h;
         int rc;
         if (g > 0 && (rc = dl(part, (size_t)q * g, h))) return rc;
@@ -1942,28 +1992,20 @@ template <typename T> struct Solver final : SolverBase {
         return BA_OK;
     }
     // the three sums of the last linearisation's partials
-    int prior_energy(double *out3) override { return kept_energy(d_part_pr.p, 3, gP, out3); }
+    int prior_energy(double *out3) override { return kept_energy(pr.part.p, 3, pr.g, out3); }
 
     // ---- relative-pose constraints (ba_solver_set_relative_poses; ba_relpose.hip.h) -------------------------------
     // The lists, the per-constraint records and the CSR of every camera's incident constraints (built here, list order); the block
-    // partials of k_relpose live behind the priors' in d_part_e (2 gR).  No constraint: no buffer, gR = 0, not one launch more.
-    DevBuf<int> d_rp_pair, d_rp_ptr, d_rp_inc;
-    DevBuf<T> d_rp_R0, d_rp_t0, d_rp_Lr, d_rp_Lt, d_rp_rec, d_part_rp; // d_part_rp: [2][gR] energies of the last linearisation
-    int n_rp = 0, gR = 0;
-    bool relposes() const { return n_rp > 0; }
-    size_t relpose_bytes() const
-    {
-        return bytes_of(d_rp_pair) + bytes_of(d_rp_ptr) + bytes_of(d_rp_inc) + bytes_of(d_rp_R0) + bytes_of(d_rp_t0) + bytes_of(d_rp_Lr) +
-               bytes_of(d_rp_Lt) + bytes_of(d_rp_rec) + bytes_of(d_part_rp);
-    }
-    ba_relpose_csr<T> relpose_csr() const { return ba_relpose_csr<T>{d_rp_ptr.p, d_rp_inc.p, d_rp_pair.p, d_rp_rec.p}; }
+    // partials of k_relpose live behind the priors' in d_part_e.  No constraint: no buffer, rp.g = 0, not one launch more.
+    bool relposes() const { return rp.n > 0; }
+    ba_relpose_csr<T> relpose_csr() const { return ba_relpose_csr<T>{rp.ptr.p, rp.inc.p, rp.pair.p, rp.rec.p}; }
     // lin: the linearisation part (records, then the gather into V / gc of the state `which`); else the energy at xTest alone
     void launch_relpose(bool lin, int which, const int *go)
     {
-        ba_relpose_args<T> ra{n_rp, d_rp_pair.p, d_rp_R0.p, d_rp_t0.p, d_rp_Lr.p, d_rp_Lt.p};
-        with_flags(lin, masked && d_cmask.p, [&](auto LIN, auto MASKED) { // (MASK = LIN && ..., as in launch_prior)
-            hipLaunchKernelGGL((k_relpose<T, LIN(), LIN() && MASKED()>), dim3(gR), dim3(256), 0, st, ra, N, (const T *)d_cam[which].p, d_rp_rec.p,
-                               d_part_e.p + gE + 3 * gP, d_part_rp.p, go, (const unsigned short *)d_cmask.p);
+        ba_relpose_args<T> ra{rp.n, rp.pair.p, rp.R0.p, rp.t0.p, rp.Lr.p, rp.Lt.p};
+        with_flags(lin, mk.on && mk.cmask.p, [&](auto LIN, auto MASKED) { // (MASK = LIN && ..., as in launch_prior)
+            hipLaunchKernelGGL((k_relpose<T, LIN(), LIN() && MASKED()>), dim3(rp.g), dim3(256), 0, st, ra, N, (const T *)d_cam[which].p, rp.rec.p,
+                               part_e_relposes(), rp.part.p, go, (const unsigned short *)mk.cmask.p);
         });
         if (!lin) return;
         hipLaunchKernelGGL((k_relpose_gather<T>), dim3((unsigned)(((size_t)N * BA_RP_ENT + 255) / 256)), dim3(256), 0, st, N, relpose_csr(), d_V.p, d_gc.p, go);
@@ -1982,12 +2024,8 @@ template <typename T> struct Solver final : SolverBase {
             std::sort(seen.begin(), seen.end());
             if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return BA_ERR_ARG; // (an unordered pair listed twice)
         }
-        auto finite = [](const double *v, size_t cnt) {
-            for (size_t q = 0; q < cnt; q++)
-                if (!std::isfinite(v[q]) || !std::isfinite((T)v[q])) return false;
-            return true;
-        };
-        if (n > 0 && !(finite(R0, (size_t)9 * n) && finite(t0, (size_t)3 * n) && finite(Lr, (size_t)9 * n) && finite(Lt, (size_t)9 * n))) return BA_ERR_ARG;
+        if (n > 0 && !(finite_in_T(R0, (size_t)9 * n) && finite_in_T(t0, (size_t)3 * n) && finite_in_T(Lr, (size_t)9 * n) && finite_in_T(Lt, (size_t)9 * n)))
+            return BA_ERR_ARG;
         for (int q = 0; q < n; q++) { // R0 a rotation
             const double *R = R0 + 9 * (size_t)q;
             double dev = 0;
@@ -1998,44 +2036,35 @@ template <typename T> struct Solver final : SolverBase {
             if (!(dev <= 1e-6) || !(det > 0)) return BA_ERR_ARG;
         }
         HIPCHK(hipStreamSynchronize(st));
-        const int gr_new = (n + 255) / 256;
         int rc;
         // everything that can fail first: the solver is unchanged behind an error
-        DevBuf<int> npair, nptr, ninc;
-        DevBuf<T> nR0, nt0, nLr, nLt, nrec, npe, npr;
+        RelPoses nr;
+        nr.n = n; nr.g = (n + 255) / 256;
+        nr.h_pair.assign(pairs, pairs + 2 * (size_t)n);
         if (n > 0) {
-            std::vector<int> hp(pairs, pairs + 2 * (size_t)n), ptr, inc;
+            std::vector<int> ptr, inc;
             ba_plan_relpose_csr(N, n, pairs, ptr, inc);
             auto conv = [](const double *v, size_t cnt) { std::vector<T> h(cnt); for (size_t q = 0; q < cnt; q++) h[q] = (T)v[q]; return h; };
-            if ((rc = npair.upload(hp)) || (rc = nptr.upload(ptr)) || (rc = ninc.upload(inc)) || (rc = nR0.upload(conv(R0, (size_t)9 * n))) ||
-                (rc = nt0.upload(conv(t0, (size_t)3 * n))) || (rc = nLr.upload(conv(Lr, (size_t)9 * n))) || (rc = nLt.upload(conv(Lt, (size_t)9 * n))) ||
-                (rc = nrec.alloc((size_t)BA_RP_REC * n))) { (void)hipGetLastError(); return rc; }
-            HIPCHK(hipMemset(nrec.p, 0, sizeof(T) * nrec.n));
+            if ((rc = nr.pair.upload(nr.h_pair)) || (rc = nr.ptr.upload(ptr)) || (rc = nr.inc.upload(inc)) || (rc = nr.R0.upload(conv(R0, (size_t)9 * n))) ||
+                (rc = nr.t0.upload(conv(t0, (size_t)3 * n))) || (rc = nr.Lr.upload(conv(Lr, (size_t)9 * n))) || (rc = nr.Lt.upload(conv(Lt, (size_t)9 * n))) ||
+                (rc = nr.rec.alloc((size_t)BA_RP_REC * n)) || (rc = nr.part.alloc(2 * (size_t)nr.g))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(nr.rec.p, 0, sizeof(T) * nr.rec.n));
+            HIPCHK(hipMemset(nr.part.p, 0, sizeof(T) * nr.part.n));
         }
-        std::vector<int> new_pairs(pairs, pairs + 2 * (size_t)n);
         Forest nf; // (ba_solver_set_preconditioner in front of this call: the forest of the new list)
-        if (iterative() && (rc = build_forest(new_pairs, precond_kind, precond_max_tree, nf))) return rc;
-        if (gr_new != gR) {
-            if ((rc = npe.alloc((size_t)gE + 3 * (size_t)gP + 2 * (size_t)gr_new)) || (rc = npr.alloc(2 * (size_t)gr_new))) { (void)hipGetLastError(); return rc; }
-            HIPCHK(hipMemset(npe.p, 0, sizeof(T) * npe.n));
-            if (npr.p) HIPCHK(hipMemset(npr.p, 0, sizeof(T) * npr.n));
-            d_part_e.swap(npe); d_part_rp.swap(npr);
-            gR = gr_new;
-        }
-        d_rp_pair.swap(npair); d_rp_ptr.swap(nptr); d_rp_inc.swap(ninc); d_rp_R0.swap(nR0); d_rp_t0.swap(nt0);
-        d_rp_Lr.swap(nLr); d_rp_Lt.swap(nLt); d_rp_rec.swap(nrec);
-        n_rp = n;
-        fo.swap(nf);
-        h_rp_pair.swap(new_pairs);
-        return model_changed(); // (the old buffers leave with the locals)
+        if (iterative() && (rc = build_forest(nr.h_pair, precond_kind, precond_max_tree, nf))) return rc;
+        if (nr.g != rp.g && (rc = resize_partials(pr.g, nr.g))) return rc;
+        rp = std::move(nr);
+        fo = std::move(nf);
+        return model_changed();
     }
     // {sum |e_r|^2, sum |e_t|^2} of the last linearisation's partials
-    int relpose_energy(double *out2) override { return kept_energy(d_part_rp.p, 2, gR, out2); }
+    int relpose_energy(double *out2) override { return kept_energy(rp.part.p, 2, rp.g, out2); }
 
     ba_red_jobs test_energy_jobs() const
     {
         ba_red_jobs jobs{};
-        jobs.j[0] = {d_part_e.p, gE + 3 * gP + 2 * gR, 0, SC_ETEST}; // (gP = 0 without priors, gR = 0 without constraints)
+        jobs.j[0] = {d_part_e.p, part_e_n(), 0, SC_ETEST};
         jobs.j[1] = {d_part_bs.p, gB, 0, SC_RHO_P};
         jobs.j[2] = {d_part_bs.p + gB, gB, 0, SC_DN_P};
         return jobs;
@@ -2075,7 +2104,7 @@ template <typename T> struct Solver final : SolverBase {
     // solve in fp64 on one shard; every other configuration keeps the head in front of every trial.
     bool tail_prepares() const
     {
-        return !trial_head && kind == BA_CHOLESKY && sizeof(T) == 8 && fused_records() && !sharded() && !relposes() && !masked && post_folded() &&
+        return !trial_head && kind == BA_CHOLESKY && sizeof(T) == 8 && fused_records() && !sharded() && !relposes() && !mk.on && post_folded() &&
                sx.nchunks > 0 && sx.ndchunks > 0;
     }
     // a phase boundary of try_step's timing (ba_timing); nothing in a captured segment
@@ -2114,15 +2143,15 @@ template <typename T> struct Solver final : SolverBase {
         }
         if ((rc = mark(EV_T4))) return rc;
         launch_backsub_retract();
-        if (d_pr_lonely.n > 0) { // (points with a prior and no observation: none on a usual problem, no launch then)
-            with_flag(masked, [&](auto MASKED) { // (two kernels, not two instantiations of one: the Marquardt one takes the bounds)
-                const unsigned char *pfix = MASKED() ? (const unsigned char *)d_pfix.p : nullptr;
+        if (pr.lonely.n > 0) { // (points with a prior and no observation: none on a usual problem, no launch then)
+            with_flag(mk.on, [&](auto MASKED) { // (two kernels, not two instantiations of one: the Marquardt one takes the bounds)
+                const unsigned char *pfix = MASKED() ? (const unsigned char *)mk.pfix.p : nullptr;
                 if (marq())
-                    hipLaunchKernelGGL((k_prior_lonely_marq<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml,
+                    hipLaunchKernelGGL((k_prior_lonely_marq<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)pr.lonely.n, (const int *)pr.lonely.p, Ml,
                                        (const T *)d_U0.p, (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p,
                                        d_part_bs.p, gB, pfix, damp_args());
                 else
-                    hipLaunchKernelGGL((k_prior_lonely<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)d_pr_lonely.n, (const int *)d_pr_lonely.p, Ml,
+                    hipLaunchKernelGGL((k_prior_lonely<T, MASKED()>), dim3(1), dim3(256), 0, st, (int)pr.lonely.n, (const int *)pr.lonely.p, Ml,
                                        (const T *)d_U0.p, (const T *)d_gp.p, (const T *)(d_scal.p + SC_LAMBDA), (const T *)d_pts[0].p, d_dxp.p, d_pts[1].p,
                                        d_part_bs.p, gB, pfix);
             });
@@ -2149,7 +2178,7 @@ template <typename T> struct Solver final : SolverBase {
     int try_step(double lambda_d, double *e_test, double *rho_scale, double *dx_norm) override
     {
         int rc;
-        if (mask_pending) return BA_ERR_ARG; // (the linearisation in place was made under another mask)
+        if (vf.mask_pending) return BA_ERR_ARG; // (the linearisation in place was made under another mask)
         if ((rc = set_lambda((T)lambda_d))) return rc;
         HIPCHK(hipEventRecord(ev[EV_T0], st));
         step_level = true;
@@ -2171,40 +2200,35 @@ template <typename T> struct Solver final : SolverBase {
         if (e_test) *e_test = (double)h_scal[SC_ETEST];
         if (rho_scale) *rho_scale = (double)(h_scal[SC_RHO_P] + h_scal[SC_RHO_C]);
         if (dx_norm) *dx_norm = std::sqrt((double)(h_scal[SC_DN_P] + h_scal[SC_DN_C]));
-        have_step = true;
+        vf.stepped();
         return BA_OK;
     }
 
     // x = xTest (BacktrackLevMarqQRChol.h:428)
     int accept() override
     {
-        if (!have_step) return BA_ERR_ARG;
-        cov_valid = false;
-        dl_valid = false;
+        if (!vf.have_step) return BA_ERR_ARG;
+        vf.results_dropped(); // (have_lin stays: J is still the old x's, and ba_solver_try_step is not refused behind an accept)
         const int ncam = 15 * N, npts = 3 * Ml;
         hipLaunchKernelGGL((k_commit<T>), dim3((ncam + npts + 255) / 256), dim3(256), 0, st, ncam, npts, d_cam[1].p, d_pts[1].p, d_cam[0].p, d_pts[0].p,
                            (const int *)nullptr);
         HIPCHK(hipStreamSynchronize(st));
-        have_step = false;
+        vf.accepted();
         return BA_OK;
     }
 
     // ---- Powell's dogleg (ba_solver_dogleg_prepare / ba_solver_try_dogleg / ba_minimize_dogleg; ba_dogleg.hip.h) --
-    // State of its own: the copy of dx_gn [3 Ml + D] and one fp64 buffer [q partials: gK | g2, gn2, g'dx_gn partials: 3 dl_gd() |
-    // |dx|^2 partials: gM + 1 | the eight sums], both allocated by the first prepare; the scalars of the last prepare on the host.
-    DevBuf<T> d_dl_keep;
-    DevBuf<double> d_dl_part;
-    bool dl_valid = false; // a prepared dogleg of the linearisation in place: cleared where cov_valid is
-    ba_dogleg_info dli{};
+    // State of its own (Dogleg dg): the copy of dx_gn and one fp64 buffer of partials and sums, both allocated by the first prepare;
+    // the scalars of the last prepare on the host.
     enum { DL_Q = 0, DL_G2, DL_GN2, DL_D, DL_DN, DL_NOUT = 8 };
     int dl_gd() const { return (int)(((size_t)3 * Ml + D + 255) / 256); }
-    double *dl_part_q() const { return d_dl_part.p; }
-    double *dl_part_dots() const { return d_dl_part.p + gK; }
+    double *dl_part_q() const { return dg.part.p; }
+    double *dl_part_dots() const { return dg.part.p + gK; }
     double *dl_part_dn() const { return dl_part_dots() + 3 * (size_t)dl_gd(); }
     double *dl_out() const { return dl_part_dn() + gM + 1; }
     // what every dogleg call refuses, the solver unchanged
     bool dogleg_kind_ok() const { return kind == BA_CHOLESKY && !sharded() && !priors() && !relposes() && damp_kind != BA_DAMP_MARQUARDT; }
-    bool dogleg_ok() const { return dogleg_kind_ok() && have_lin && !mask_pending; }
+    bool dogleg_ok() const { return dogleg_kind_ok() && vf.have_lin && !vf.mask_pending; }
     int dl_fetch(double *h)
     {
         HIPCHK(hipMemcpyAsync(h, dl_out(), sizeof(double) * DL_NOUT, hipMemcpyDeviceToHost, st));
@@ -2220,20 +2244,19 @@ template <typename T> struct Solver final : SolverBase {
 
     int dogleg_prepare(double mu, ba_dogleg_info *out) override
     {
-        if (!dogleg_ok() || !(mu > 0) || !std::isfinite(mu) || !((T)mu > 0) || !std::isfinite((T)mu)) return BA_ERR_ARG;
+        if (!dogleg_ok() || !positive_in_T(mu)) return BA_ERR_ARG;
         int rc;
-        if (!d_dl_keep.p || !d_dl_part.p) {
-            DevBuf<T> nk;
-            DevBuf<double> np;
-            if ((rc = nk.alloc((size_t)3 * Ml + D)) || (rc = np.alloc((size_t)gK + 3 * (size_t)dl_gd() + gM + 1 + DL_NOUT))) { (void)hipGetLastError(); return rc; }
-            HIPCHK(hipMemset(np.p, 0, sizeof(double) * np.n));
-            d_dl_keep.swap(nk); d_dl_part.swap(np);
+        if (!dg.keep.p || !dg.part.p) {
+            Dogleg nd;
+            if ((rc = nd.keep.alloc((size_t)3 * Ml + D)) || (rc = nd.part.alloc((size_t)gK + 3 * (size_t)dl_gd() + gM + 1 + DL_NOUT))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(nd.part.p, 0, sizeof(double) * nd.part.n));
+            dg = std::move(nd);
         }
-        dl_valid = false;
+        vf.dogleg_dropped();
         double e_gn = 0, rs_gn = 0;
         if ((rc = try_step(mu, &e_gn, &rs_gn, nullptr))) return rc;
         hipLaunchKernelGGL((k_dogleg_dots<T>), dim3(dl_gd()), dim3(256), 0, st, 3 * Ml, D, (const T *)d_gp.p, (const T *)d_gc.p, (const T *)d_dxp.p,
-                           (const T *)d_dxc.p, d_dl_keep.p, dl_part_dots());
+                           (const T *)d_dxc.p, dg.keep.p, dl_part_dots());
         launch_jg();
         ba_red_jobs jobs{};
         jobs.j[0] = {dl_part_q(), gK, 0, DL_Q};
@@ -2242,25 +2265,25 @@ template <typename T> struct Solver final : SolverBase {
         double h[DL_NOUT];
         if ((rc = dl_fetch(h))) return rc;
         HIPCHK(hipGetLastError());
-        dli.mu = mu; dli.g2 = h[DL_G2]; dli.q = h[DL_Q]; dli.gn2 = h[DL_GN2]; dli.g_dot_gn = h[DL_D];
-        dli.alpha = dli.g2 > 0 ? dli.g2 / dli.q : 0.0;
-        dli.energy_gn = e_gn; dli.rho_scale_gn = rs_gn;
-        dl_valid = true;
-        if (out) *out = dli;
+        dg.info.mu = mu; dg.info.g2 = h[DL_G2]; dg.info.q = h[DL_Q]; dg.info.gn2 = h[DL_GN2]; dg.info.g_dot_gn = h[DL_D];
+        dg.info.alpha = dg.info.g2 > 0 ? dg.info.g2 / dg.info.q : 0.0;
+        dg.info.energy_gn = e_gn; dg.info.rho_scale_gn = rs_gn;
+        vf.dogleg_prepared();
+        if (out) *out = dg.info;
         return BA_OK;
     }
 
     int try_dogleg(double radius, double *e_test, double *pred, double *dx_norm, int *branch) override
     {
-        if (!dogleg_ok() || !dl_valid || !(radius > 0)) return BA_ERR_ARG;
-        double a = 0, c = 0, pr = 0;
+        if (!dogleg_ok() || !vf.dl_valid || !(radius > 0)) return BA_ERR_ARG;
+        double a = 0, c = 0, pred_v = 0;
         int br = 0, rc;
-        if ((rc = ba_dogleg_coefficients(dli.g2, dli.q, dli.gn2, dli.g_dot_gn, dli.mu, radius, &a, &c, &br, &pr))) return rc;
+        if ((rc = ba_dogleg_coefficients(dg.info.g2, dg.info.q, dg.info.gn2, dg.info.g_dot_gn, dg.info.mu, radius, &a, &c, &br, &pred_v))) return rc;
         const ba_cam_retract_args cr{N, d_cam[0].p, d_dxc.p, d_gcg.p, d_cam[1].p, d_scal.p, (int)SC_RHO_C};
-        with_flag(masked, [&](auto MASKED) {
+        with_flag(mk.on, [&](auto MASKED) {
             hipLaunchKernelGGL((k_dogleg_step<T, MASKED()>), dim3(gM + 1), dim3(256), 0, st, Ml, gM, (T)a, (T)c, (const int *)d_pt_ptr.p, (const T *)d_gp.p,
-                               (const T *)d_gc.p, (const T *)d_dl_keep.p, (const T *)d_pts[0].p, d_dxp.p, d_dxc.p, d_pts[1].p,
-                               (const T *)(d_scal.p + SC_LAMBDA), dl_part_dn(), cr, ba_fix_args{d_cmask.p, d_pfix.p});
+                               (const T *)d_gc.p, (const T *)dg.keep.p, (const T *)d_pts[0].p, d_dxp.p, d_dxc.p, d_pts[1].p,
+                               (const T *)(d_scal.p + SC_LAMBDA), dl_part_dn(), cr, ba_fix_args{mk.cmask.p, mk.pfix.p});
         });
         launch_test_energy();
         ba_red_jobs jobs{};
@@ -2270,10 +2293,10 @@ template <typename T> struct Solver final : SolverBase {
         if ((rc = fetch_scalars()) || (rc = dl_fetch(h))) return rc;
         HIPCHK(hipGetLastError());
         if (e_test) *e_test = (double)h_scal[SC_ETEST];
-        if (pred) *pred = pr;
+        if (pred) *pred = pred_v;
         if (dx_norm) *dx_norm = std::sqrt(h[DL_DN]);
         if (branch) *branch = br;
-        have_step = true;
+        vf.stepped();
         return BA_OK;
     }
 
@@ -2354,10 +2377,7 @@ template <typename T> struct Solver final : SolverBase {
             }
         }
         if (talk) printf("--------------------------------------------------------------------------------\n");
-        have_step = false;
-        cov_valid = false;
-        dl_valid = false;
-        have_lin = false; // (as behind ba_minimize: a ba_solver_linearize at the final x comes first)
+        vf.x_moved(); // (as behind ba_minimize)
         if (out) {
             out->status = status; out->iterations = iter; out->trials = trials; out->fun_evals = fun_evals;
             out->energy = E; out->lambda = radius;
@@ -2370,91 +2390,72 @@ template <typename T> struct Solver final : SolverBase {
     }
 
     // ---- triangulation (ba_solver_triangulate_points; ba_triangulate.hip.h) -------------------------------------
-    // Buffers of its own, all allocated by the first call: the rays [3][Kl] fp64, status / request / fixed flags [Ml] each, and one fp64
-    // buffer [block partials: 10 tri_gmax() | the ten sums, padded to 16].
-    DevBuf<double> d_tri_ray, d_tri_part;
-    DevBuf<int> d_tri_ids;
-    DevBuf<unsigned char> d_tri_stat, d_tri_fix;
-    bool model_pending = false; // ba_solver_set_loss / _set_obs_weights since the last linearisation
+    // Buffers of its own (Triang tr), all allocated by the first call.
     enum { TRI_LANES = 8, TRI_NSUM = 10 };
     int tri_gmax() const { return std::max(1, (int)(((size_t)Ml * TRI_LANES + 255) / 256)); }
-    size_t tri_bytes() const { return bytes_of(d_tri_ray) + bytes_of(d_tri_part) + bytes_of(d_tri_ids) + bytes_of(d_tri_stat) + bytes_of(d_tri_fix); }
 
     int triangulate(const ba_triangulate_params *pp, int n_pts, const int *pt_ids, unsigned char *status, ba_triangulate_stats *stats) override
     {
         ba_triangulate_params tp;
         if (pp) tp = *pp; else ba_triangulate_params_default(&tp);
-        if (sharded() || ba_triangulate_params_check(&tp) || n_pts < 0 || (!pt_ids && n_pts > 0) || model_pending) return BA_ERR_ARG;
+        if (sharded() || ba_triangulate_params_check(&tp) || n_pts < 0 || (!pt_ids && n_pts > 0) || vf.model_pending) return BA_ERR_ARG;
         const int n = pt_ids ? n_pts : Ml;
-        if (n > Ml) return BA_ERR_ARG; // (some id is listed twice)
-        if (pt_ids) {
-            std::vector<char> seen((size_t)(Ml > 0 ? Ml : 1), 0);
-            for (int q = 0; q < n; q++) {
-                if (pt_ids[q] < 0 || pt_ids[q] >= Ml || seen[pt_ids[q]]) return BA_ERR_ARG;
-                seen[pt_ids[q]] = 1;
-            }
-        }
+        if (pt_ids && !distinct_ids(n, pt_ids, Ml)) return BA_ERR_ARG;
         int rc;
-        if (!d_tri_part.p) { // everything that can fail first: the solver is unchanged behind an error
-            DevBuf<double> nr, np;
-            DevBuf<int> ni;
-            DevBuf<unsigned char> ns, nf;
+        if (!tr.part.p) { // everything that can fail first: the solver is unchanged behind an error
+            Triang nt;
             const size_t m1 = (size_t)(Ml > 0 ? Ml : 1);
-            if ((rc = nr.alloc((size_t)3 * (Kl > 0 ? Kl : 1))) || (rc = np.alloc((size_t)TRI_NSUM * tri_gmax() + 16)) || (rc = ni.alloc(m1)) ||
-                (rc = ns.alloc(m1)) || (rc = nf.alloc(m1))) { (void)hipGetLastError(); return rc; }
-            HIPCHK(hipMemset(np.p, 0, sizeof(double) * np.n));
-            d_tri_ray.swap(nr); d_tri_part.swap(np); d_tri_ids.swap(ni); d_tri_stat.swap(ns); d_tri_fix.swap(nf);
+            if ((rc = nt.ray.alloc((size_t)3 * (Kl > 0 ? Kl : 1))) || (rc = nt.part.alloc((size_t)TRI_NSUM * tri_gmax() + 16)) || (rc = nt.ids.alloc(m1)) ||
+                (rc = nt.stat.alloc(m1)) || (rc = nt.fix.alloc(m1))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(nt.part.p, 0, sizeof(double) * nt.part.n));
+            tr = std::move(nt);
         }
         HIPCHK(hipStreamSynchronize(st));
         ba_triangulate_stats ts{};
         ts.asked = n;
         if (n > 0) {
             // a point held constant or carrying a prior is never touched
-            const bool any_fix = (masked && d_pfix.p) || n_pr[0] > 0;
+            const bool any_fix = (mk.on && mk.pfix.p) || pr.of[0].n > 0;
             if (any_fix) {
                 std::vector<unsigned char> hf((size_t)Ml, 0);
-                if (masked && d_pfix.p) HIPCHK(hipMemcpy(hf.data(), d_pfix.p, (size_t)Ml, hipMemcpyDeviceToHost));
-                if (n_pr[0] > 0) {
-                    std::vector<int> hid((size_t)n_pr[0]);
-                    HIPCHK(hipMemcpy(hid.data(), d_pr_id[0].p, sizeof(int) * hid.size(), hipMemcpyDeviceToHost));
+                if (mk.on && mk.pfix.p) HIPCHK(hipMemcpy(hf.data(), mk.pfix.p, (size_t)Ml, hipMemcpyDeviceToHost));
+                if (pr.of[0].n > 0) {
+                    std::vector<int> hid((size_t)pr.of[0].n);
+                    HIPCHK(hipMemcpy(hid.data(), pr.of[0].id.p, sizeof(int) * hid.size(), hipMemcpyDeviceToHost));
                     for (int id : hid) hf[id] = 1;
                 }
-                HIPCHK(hipMemcpy(d_tri_fix.p, hf.data(), hf.size(), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(tr.fix.p, hf.data(), hf.size(), hipMemcpyHostToDevice));
             }
-            if (pt_ids) HIPCHK(hipMemcpy(d_tri_ids.p, pt_ids, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-            const int *ids = pt_ids ? (const int *)d_tri_ids.p : nullptr;
+            if (pt_ids) HIPCHK(hipMemcpy(tr.ids.p, pt_ids, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+            const int *ids = pt_ids ? (const int *)tr.ids.p : nullptr;
             const int g = (int)(((size_t)n * TRI_LANES + 255) / 256);
-            const ba_tri_cfg cf{tp.min_angle_deg * (M_PI / 180.0), tp.max_reproj_px, tp.refine_iters, tp.only_if_better, loss_kind, (double)loss_scale};
-            double *sums = d_tri_part.p + (size_t)TRI_NSUM * tri_gmax();
+            const ba_tri_cfg cf{tp.min_angle_deg * (M_PI / 180.0), tp.max_reproj_px, tp.refine_iters, tp.only_if_better, md.loss_kind, (double)md.loss_scale};
+            double *sums = tr.part.p + (size_t)TRI_NSUM * tri_gmax();
             HIPCHK(hipEventRecord(ev[EV_T0], st));
             hipLaunchKernelGGL((k_tri_rays<T, TRI_LANES>), dim3(g), dim3(256), 0, st, n, ids, N, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
-                               (const T *)d_cam[0].p, (const T *)d_meas.p, d_tri_ray.p);
+                               (const T *)d_cam[0].p, (const T *)d_meas.p, tr.ray.p);
             hipLaunchKernelGGL((k_tri_points<T, TRI_LANES>), dim3(g), dim3(256), 0, st, n, ids, N, Ml, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
-                               (const T *)d_cam[0].p, (const T *)d_meas.p, (const T *)d_wobs.p, (const double *)d_tri_ray.p,
-                               any_fix ? (const unsigned char *)d_tri_fix.p : (const unsigned char *)nullptr, cf, d_pts[0].p, d_tri_stat.p, d_tri_part.p);
+                               (const T *)d_cam[0].p, (const T *)d_meas.p, (const T *)md.wobs.p, (const double *)tr.ray.p,
+                               any_fix ? (const unsigned char *)tr.fix.p : (const unsigned char *)nullptr, cf, d_pts[0].p, tr.stat.p, tr.part.p);
             ba_red_jobs jobs{};
-            for (int k = 0; k < 8; k++) jobs.j[k] = {d_tri_part.p + (size_t)k * g, g, 0, k};
+            for (int k = 0; k < 8; k++) jobs.j[k] = {tr.part.p + (size_t)k * g, g, 0, k};
             hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(8), dim3(256), 0, st, jobs, sums, (const int *)nullptr, (long long *)nullptr);
             ba_red_jobs jobs2{};
-            for (int k = 0; k < 2; k++) jobs2.j[k] = {d_tri_part.p + (size_t)(8 + k) * g, g, 0, 8 + k};
+            for (int k = 0; k < 2; k++) jobs2.j[k] = {tr.part.p + (size_t)(8 + k) * g, g, 0, 8 + k};
             hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(2), dim3(256), 0, st, jobs2, sums, (const int *)nullptr, (long long *)nullptr);
             HIPCHK(hipEventRecord(ev[EV_T1], st));
             double h[TRI_NSUM];
             HIPCHK(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             HIPCHK(hipGetLastError());
-            if (status) HIPCHK(hipMemcpy(status, d_tri_stat.p, (size_t)n, hipMemcpyDeviceToHost));
+            if (status) HIPCHK(hipMemcpy(status, tr.stat.p, (size_t)n, hipMemcpyDeviceToHost));
             for (int k = 0; k < 8; k++) ts.by_status[k] = (long long)h[k];
             ts.cost_before = h[8]; ts.cost_after = h[9];
             ts.ms = ev_ms(EV_T0, EV_T1);
         }
         // what ba_solver_set_state(s, NULL, pts) invalidates; and J is another state's: ba_solver_try_step refuses until the next
         // linearisation, as it does behind a setter
-        cov_valid = false;
-        dl_valid = false;
-        have_lin = false;
-        have_step = false;
-        mask_pending = true;
+        vf.points_reseated();
         if (stats) *stats = ts;
         return BA_OK;
     }
@@ -2632,15 +2633,13 @@ template <typename T> struct Solver final : SolverBase {
         const std::vector<T> h = cam15 ? aos_to_soa(cam15, N, 15) : std::vector<T>();
         if (cam15 && share_on() && !share_equal(sh.h_gptr, sh.h_members, h.data(), N)) return BA_ERR_ARG; // (state unchanged)
         HIPCHK(hipStreamSynchronize(st));
-        cov_valid = false;
-        dl_valid = false;
-        have_lin = false; // (J is another state's)
+        vf.lin_dropped();
         if (cam15) HIPCHK(hipMemcpy(d_cam[0].p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
         if (pts && Ml > 0) {
             const std::vector<T> hp = aos_to_soa(pts, Ml, 3);
             HIPCHK(hipMemcpy(d_pts[0].p, hp.data(), sizeof(T) * hp.size(), hipMemcpyHostToDevice));
         }
-        have_step = false;
+        vf.step_dropped();
         return BA_OK;
     }
 
@@ -2892,10 +2891,7 @@ template <typename T> struct Solver final : SolverBase {
             HIPCHK(hipGetLastError());
         }
         if (talk) printf("--------------------------------------------------------------------------------\n");
-        have_step = false;
-        cov_valid = false;
-        dl_valid = false;
-        have_lin = false; // (ba_solver_covariance_compute wants a ba_solver_linearize at the final x first)
+        vf.x_moved(); // (ba_solver_covariance_compute wants a ba_solver_linearize at the final x first)
         if (out) {
             out->status = h.status; out->iterations = h.iter; out->trials = h.trials; out->fun_evals = h.fun_evals;
             out->energy = (double)h.energy; out->lambda = (double)h.lambda;
@@ -2930,7 +2926,7 @@ template <typename T> struct Solver final : SolverBase {
         hipLaunchKernelGGL((k_fill_sentinel<T>), dim3((2 * Dp + 2 * NB + 255) / 256), dim3(256), 0, st, 2 * Dp + 2 * NB, d_dxc.p);
         hipLaunchKernelGGL((k_ldlt_backflow<T, NB>), dim3(2 * groups), dim3(256), 0, st, D, ld, D, nblk, d_S.p, d_Winv.p, d_dxc.p, d_dxc.p + Dp,
                            d_scal.p + SC_ERR, 1 << 10, groups - 1);
-        have_step = false;
+        vf.step_dropped();
         return fetch_scalars();
     }
 
@@ -2939,7 +2935,7 @@ template <typename T> struct Solver final : SolverBase {
         if (reps < 1 || !ms) return BA_ERR_ARG;
         if (iterative() && (phase == 3 || phase == 6 || phase == 7)) return BA_ERR_ARG; // (no S)
         if ((phase == 9 || phase == 10) && !(iterative() && forest_on() && (phase == 10 || fo.width == 9))) return BA_ERR_ARG;
-        if (phase == 11 && !(dogleg_ok() && d_dl_part.p)) return BA_ERR_ARG; // (k_jg writes the dogleg's partial list: a prepare comes first)
+        if (phase == 11 && !(dogleg_ok() && dg.part.p)) return BA_ERR_ARG; // (k_jg writes the dogleg's partial list: a prepare comes first)
         double acc_ms = 0;
         int rcl = set_lambda((T)lambda_d);
         if (rcl) return rcl;
@@ -3000,7 +2996,7 @@ template <typename T> struct Solver final : SolverBase {
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
         *ms = ((phase == 6 || phase == 7 || phase == 10) ? acc_ms : ev_ms(EV_T0, EV_T1)) / reps;
-        have_step = false;
+        vf.step_dropped();
         return BA_OK;
     }
 };

@@ -10,7 +10,8 @@ Problem.synthetic(300, 3000, 15000, 19) (the camera kernels run past one workgro
 Per input and scalar type, ITERSCHUR under five setups -- block Jacobi; the constraint forest over a chain of relative poses; the
 visibility forest; a constant mask; shared intrinsics -- each hashed behind try_step at two lambda (GET_RHS, GET_DX, GET_CAMS_TEST,
 GET_POINTS_TEST, pcg_stats) and over the trial rows of a five-trial minimize.  In fp64 also covariance_pcg for two camera pairs and
-four points (two point batches), plain and under the mask, and the dense covariance under CHOLESKY for the same request.
+four points (two point batches), plain and under the mask, and the dense covariance under CHOLESKY for the same request.  Every
+solver's device_bytes closes its lines, as a number.
 """
 import hashlib
 import os
@@ -77,6 +78,7 @@ def trials(ba, tag, p, scalar):
             line("%s %s lam=%g pcg_stats" % (tag, name, lam),
                  np.array([st["solves"], st["total_iters"], st["last_iters"], st["last_converged"]], np.int64), np.float64(st["last_rel_residual"]))
         line("%s %s minimize rows" % (tag, name), s.minimize(max_trials=5)["trace"][:, :5])  # (the last column is a wall-clock time)
+        print("%s %s device_bytes %d" % (tag, name, s.device_bytes()), flush=True)
 
 
 def covariances(ba, tag, p):
@@ -92,6 +94,7 @@ def covariances(ba, tag, p):
         line("%s covariance_pcg %s points" % (tag, name), pc)
         line("%s covariance_pcg %s stats" % (tag, name), np.array([st[k] for k in ("columns", "batches", "total_iters", "max_iters", "unconverged")], np.int64),
              np.float64(st["worst_rel_residual"]))
+        print("%s covariance_pcg %s device_bytes %d" % (tag, name, s.device_bytes()), flush=True)
         d = ba.Solver(p, ba.CHOLESKY, ba.F64)
         if masked:
             d.set_constant(*mask(ba, p))
@@ -99,6 +102,7 @@ def covariances(ba, tag, p):
         cc, pc = d.covariance(1e-4 * dmax, cam_pairs=pairs, points=pts)
         line("%s covariance dense %s cameras" % (tag, name), cc)
         line("%s covariance dense %s points" % (tag, name), pc)
+        print("%s covariance dense %s device_bytes %d" % (tag, name, d.device_bytes()), flush=True)
 
 
 def main():

@@ -17,6 +17,12 @@ Per case (CASES: the fewest that reach every branch of the solver's launch state
                          scalars, GET_DX, GET_CAMS_TEST, GET_POINTS_TEST
   time_phase(1), (8)     one linearisation by the separate launches, one by the fused pass: GET_RESIDUALS, GET_JC, GET_JP, GET_GRAD
   minimize(max_trials=5) the trial rows, the result and the final state (the graph path: fused linearisation, x = xTest on k_eval)
+  device_bytes           at the end, as a number
+The plain CHOLESKY case also: dogleg_prepare at LAMS[1] x max diag J'J (its scalars), try_dogleg at half and at twice the Gauss-Newton
+norm (the scalars and GET_DX) behind the try_steps, and at the end triangulate_points on all points (status bytes, the stats without
+the time, GET_POINTS).  "priors+relpose" has both optional terms in the partial buffers; "priors_resize" sets the priors, then a point
+list of another block count (k_prior has one workgroup per 256 priors), then none at all, with a linearisation behind each, and goes
+on as the plain case.
 """
 import os
 import sys
@@ -40,6 +46,8 @@ CASES = (
     ("CHOLESKY", ("priors", "marq", "mask"), {}),
     ("CHOLESKY", ("relpose",), {}),
     ("CHOLESKY", ("relpose", "mask"), {}),
+    ("CHOLESKY", ("priors", "relpose"), {}),
+    ("CHOLESKY", ("priors_resize",), {}),
     ("CHOLESKY", ("marq",), {"BA_NO_FOLD": "1"}),  # the only route to the stand-alone k_post_reduce<T, true>
     ("ITERSCHUR", ("marq",), {}),
     ("ITERSCHUR", ("marq", "mask"), {}),
@@ -73,6 +81,28 @@ def priors(ba, s, p):
     s.set_intrinsics_priors(iids, cams[iids, 12:15] * 1.001, sigma=np.abs(cams[iids, 12:15]) * 0.01 + 1e-9)
 
 
+def priors_resize(ba, s, p, tag):
+    none = np.zeros(0, np.int32)
+    priors(ba, s, p)
+    for name, ids in (("set", None), ("700 points", np.arange(0, 2100, 3, dtype=np.int32)), ("no points", none), ("none", none)):
+        if ids is not None:
+            s.set_point_priors(ids, s.get(ba.GET_POINTS).reshape(p.M, 3)[ids] + 0.01, sigma=0.1)
+        if name == "none":
+            s.set_centre_priors(none, np.zeros((0, 3)), sigma=1.0)
+            s.set_intrinsics_priors(none, np.zeros((0, 3)), sigma=1.0)
+        line("%s priors %s linearize" % (tag, name), np.float64(s.linearize()), s.prior_energy())
+        print("%s priors %s device_bytes %d" % (tag, name, s.device_bytes()), flush=True)
+
+
+def dogleg(ba, s, tag, mu):
+    info = s.dogleg_prepare(mu)
+    line("%s dogleg_prepare" % tag, np.float64([info[k] for k in ("mu", "g2", "q", "gn2", "g_dot_gn", "alpha", "energy_gn", "rho_scale_gn")]))
+    for f in (0.5, 2.0):  # inside the Gauss-Newton norm (the interpolated or the gradient step), outside it (the Gauss-Newton step)
+        e, pred, dxn, branch = s.try_dogleg(f * np.sqrt(info["gn2"]))
+        line("%s try_dogleg %g |gn|" % (tag, f), np.float64([e, pred, dxn]), np.int64(branch))
+        line("%s try_dogleg %g |gn| GET_DX" % (tag, f), s.get(ba.GET_DX))
+
+
 def setup(ba, s, p, opts):
     if "model" in opts:  # Huber away from the default scale, weights that are exact in fp32
         s.set_loss(ba.LOSS_HUBER, 1.0)
@@ -95,6 +125,9 @@ def case(ba, tag, p, kind, opts, env):
         for k in env:
             del os.environ[k]
     tag = " ".join([tag, kind, "+".join(opts) or "plain"] + ["%s=%s" % kv for kv in env.items()])
+    plain = kind == "CHOLESKY" and not opts and not env
+    if "priors_resize" in opts:
+        priors_resize(ba, s, p, tag)
     setup(ba, s, p, opts)
     e, dmax = s.linearize()
     line("%s linearize" % tag, np.float64([e, dmax]))
@@ -107,6 +140,8 @@ def case(ba, tag, p, kind, opts, env):
         line("%s lam=%g try_step" % (tag, lam), np.float64(s.try_step(lam * scale)))
         for what in ("GET_DX", "GET_CAMS_TEST", "GET_POINTS_TEST"):
             line("%s lam=%g %s" % (tag, lam, what), s.get(getattr(ba, what)))
+    if plain:
+        dogleg(ba, s, tag, LAMS[1] * dmax)
     for phase in (1, 8):
         s.time_phase(phase, 1, LAMS[0] * scale)
         for what in ("GET_RESIDUALS", "GET_JC", "GET_JP", "GET_GRAD"):
@@ -115,6 +150,11 @@ def case(ba, tag, p, kind, opts, env):
     line("%s minimize rows" % tag, r["trace"][:, :5])  # (the last column is a wall-clock time)
     line("%s minimize result" % tag, np.int64([r["status"], r["iterations"], r["trials"], r["fun_evals"]]), np.float64([r["energy"], r["lam"]]))
     line("%s minimize state" % tag, s.get(ba.GET_CAMS), s.get(ba.GET_POINTS))
+    if plain:
+        ts, status = s.triangulate_points()
+        line("%s triangulate_points" % tag, status, np.int64(ts["asked"]), ts["by_status"], np.float64([ts["cost_before"], ts["cost_after"]]))
+        line("%s triangulate_points GET_POINTS" % tag, s.get(ba.GET_POINTS))
+    print("%s device_bytes %d" % (tag, s.device_bytes()), flush=True)
 
 
 def main():

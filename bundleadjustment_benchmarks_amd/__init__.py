@@ -54,10 +54,16 @@ EXPORTS = [
     "ba_solver_set_pcg_model_tol", "ba_solver_pcg_stop_stats",
     "ba_dogleg_coefficients", "ba_solver_dogleg_prepare", "ba_solver_try_dogleg", "ba_dogleg_params_default", "ba_minimize_dogleg",
     "ba_triangulate_params_default", "ba_solver_triangulate_points", "ba_triangulate_point",
+    "ba_solver_set_obs_active", "ba_solver_get_obs_active", "ba_filter_params_default", "ba_solver_filter_observations", "ba_filter_track",
 ]
 # ba_triangulate_status (include/ba_mi355x.h)
 TRI_REPLACED, TRI_FEW_VIEWS, TRI_LOW_ANGLE, TRI_DEGENERATE, TRI_BEHIND, TRI_REPROJ, TRI_NOT_BETTER, TRI_FIXED = range(8)
 TRI_NAMES = ("REPLACED", "FEW_VIEWS", "LOW_ANGLE", "DEGENERATE", "BEHIND", "REPROJ", "NOT_BETTER", "FIXED")
+# ba_obs_status, ba_filter_point_status (include/ba_mi355x.h)
+OBS_KEPT, OBS_WAS_OFF, OBS_BEHIND, OBS_NONFINITE, OBS_REPROJ, OBS_POINT = range(6)
+OBS_NAMES = ("KEPT", "WAS_OFF", "BEHIND", "NONFINITE", "REPROJ", "POINT")
+FPT_KEPT, FPT_SHORT, FPT_LOW_ANGLE = range(3)
+FPT_NAMES = ("KEPT", "SHORT", "LOW_ANGLE")
 ERR_ARG, ERR_NOMEM, ERR_SINGULAR = 4, 6, 8
 
 
@@ -125,6 +131,35 @@ class TriangulateParams(C.Structure):
 class TriangulateStats(C.Structure):
     _fields_ = [("asked", C.c_longlong), ("by_status", C.c_longlong * 8), ("cost_before", C.c_double), ("cost_after", C.c_double),
                 ("ms", C.c_double)]
+
+
+class FilterParams(C.Structure):
+    _fields_ = [("max_reproj_px", C.c_double), ("min_angle_deg", C.c_double), ("min_track", C.c_int), ("require_front", C.c_int)]
+
+    @classmethod
+    def default(cls):
+        p = cls()
+        lib().ba_filter_params_default(C.byref(p))
+        return p
+
+
+class FilterStats(C.Structure):
+    _fields_ = [("active_before", C.c_longlong), ("active_after", C.c_longlong), ("by_status", C.c_longlong * 6),
+                ("points_short", C.c_longlong), ("points_low_angle", C.c_longlong), ("err_sum_before", C.c_double),
+                ("err_sum_after", C.c_double), ("ms", C.c_double)]
+
+
+def _filter_params(max_reproj_px, min_angle_deg, min_track, require_front):
+    fp = FilterParams.default()
+    if max_reproj_px is not None:
+        fp.max_reproj_px = float(max_reproj_px)
+    if min_angle_deg is not None:
+        fp.min_angle_deg = float(min_angle_deg)
+    if min_track is not None:
+        fp.min_track = int(min_track)
+    if require_front is not None:
+        fp.require_front = int(bool(require_front))
+    return fp
 
 
 def _tri_params(min_angle_deg, max_reproj_px, refine_iters, only_if_better):
@@ -213,6 +248,12 @@ def lib():
         L.ba_triangulate_params_default.argtypes = [C.c_void_p]
         L.ba_solver_triangulate_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         L.ba_triangulate_point.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_double] + [C.c_void_p] * 7
+        L.ba_solver_set_obs_active.argtypes = [C.c_void_p, C.c_void_p]
+        L.ba_solver_get_obs_active.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ba_filter_params_default.restype = None
+        L.ba_filter_params_default.argtypes = [C.c_void_p]
+        L.ba_solver_filter_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.ba_filter_track.argtypes = [C.c_int] + [C.c_void_p] * 9
         L.ba_solver_device_bytes.argtypes = [C.c_void_p, C.c_void_p]
         L.ba_solver_set_constant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ba_problem_gauge_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -471,6 +512,40 @@ class Solver:
                                                 C.byref(ts)), "ba_solver_triangulate_points")
         return (dict(asked=ts.asked, by_status=np.array(list(ts.by_status), np.int64), cost_before=ts.cost_before,
                      cost_after=ts.cost_after, ms=ts.ms), status[:n])
+
+    # -- the active mask and the filter (CHOLESKY and ITERSCHUR, one shard; include/ba_mi355x.h) -----------------
+    def set_obs_active(self, active=None):
+        """ba_solver_set_obs_active: K bools / bytes of the problem in the order of the input file (None: all active).  An inactive
+        observation is exactly 0 in e and J from the next linearize() / minimize() on."""
+        if active is not None:
+            active = np.ascontiguousarray(np.asarray(active) != 0, np.uint8)
+            if active.shape != (self.problem.K,):
+                raise ValueError("active must have shape (%d,), got %s" % (self.problem.K, active.shape))
+        _chk(lib().ba_solver_set_obs_active(self._h, _p(active)), "ba_solver_set_obs_active")
+
+    def get_obs_active(self):
+        """ba_solver_get_obs_active: the mask as K bools in file order."""
+        a = np.zeros(max(self.problem.K, 1), np.uint8)
+        n = C.c_longlong()
+        _chk(lib().ba_solver_get_obs_active(self._h, _p(a), C.byref(n)), "ba_solver_get_obs_active")
+        a = a[:self.problem.K].astype(bool)
+        assert int(a.sum()) == n.value
+        return a
+
+    def filter_observations(self, apply=True, max_reproj_px=None, min_angle_deg=None, min_track=None, require_front=None):
+        """ba_solver_filter_observations on the resident state: (stats dict with active_before, active_after, by_status [6],
+        points_short, points_low_angle, err_sum_before, err_sum_after, ms; obs_status uint8 [K] in file order, OBS_*; pt_status uint8
+        [M], FPT_*; err_px float64 [K] in file order).  None keeps a default of ba_filter_params_default.  With apply every observation
+        that is not OBS_KEPT becomes inactive; a linearize() comes next if one was."""
+        fp = _filter_params(max_reproj_px, min_angle_deg, min_track, require_front)
+        K, M = self.problem.K, self.problem.M
+        ost, pst, err = np.zeros(max(K, 1), np.uint8), np.zeros(max(M, 1), np.uint8), np.zeros(max(K, 1))
+        fs = FilterStats()
+        _chk(lib().ba_solver_filter_observations(self._h, C.byref(fp), int(bool(apply)), _p(ost), _p(pst), _p(err), C.byref(fs)),
+             "ba_solver_filter_observations")
+        st = {k: getattr(fs, k) for k, _ in FilterStats._fields_ if k != "by_status"}
+        st["by_status"] = np.array(list(fs.by_status), np.int64)
+        return st, ost[:K], pst[:M], err[:K]
 
     def timing(self, reset=False):
         t = Timing()
@@ -795,6 +870,25 @@ def triangulate_point(cam15, meas, x_old, w=None, loss_kind=LOSS_REFERENCE, loss
                                     int(loss_kind), float(loss_scale), C.byref(tp), _p(x_old), _p(x), C.byref(st), C.byref(c0), C.byref(c1),
                                     C.byref(ang)), "ba_triangulate_point")
     return dict(x=x, status=st.value, cost_old=c0.value, cost_new=c1.value, angle_deg=ang.value)
+
+
+def filter_track(cam15, meas, X, active=None, max_reproj_px=None, min_angle_deg=None, min_track=None, require_front=None):
+    """ba_filter_track (host only): the filter's per-point rule on one track.  cam15 [t, 15] (rows of GET_CAMS, one per observation),
+    meas [t, 2], active [t] or None: dict(obs_status uint8 [t], pt_status, err_px [t], angle_deg).  Raises BAError (ERR_ARG) for what
+    the library refuses."""
+    cam15 = np.ascontiguousarray(cam15, np.float64).reshape(-1, 15)
+    t = len(cam15)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 2)
+    X = np.ascontiguousarray(X, np.float64).reshape(3)
+    if len(meas) != t or (active is not None and np.size(active) != t):
+        raise ValueError("cam15, meas and active disagree on the track length")
+    act = None if active is None else np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, np.uint8)
+    fp = _filter_params(max_reproj_px, min_angle_deg, min_track, require_front)
+    ost, err = np.zeros(max(t, 1), np.uint8), np.zeros(max(t, 1))
+    ps, ang = C.c_int(), C.c_double()
+    _chk(lib().ba_filter_track(t, _p(cam15) if t else None, _p(meas) if t else None, None if act is None or not t else _p(act), _p(X),
+                               C.byref(fp), _p(ost), C.byref(ps), _p(err), C.byref(ang)), "ba_filter_track")
+    return dict(obs_status=ost[:t], pt_status=ps.value, err_px=err[:t], angle_deg=ang.value)
 
 
 def relative_pose(cam15, a, b):

@@ -126,6 +126,9 @@ size_t ba_plan_owner_offsets(int Dp, int nb, int world, std::vector<int> &off);
 // ba_solver_triangulate_points' and ba_triangulate_point's common refusals (ba_triangulate.cpp): BA_ERR_ARG for min_angle_deg outside
 // [0, 180), max_reproj_px < 0, refine_iters < 0 or a value that is not finite
 int ba_triangulate_params_check(const ba_triangulate_params *p);
+// ba_solver_filter_observations' and ba_filter_track's common refusals (ba_filter.cpp): BA_ERR_ARG for max_reproj_px < 0, min_angle_deg
+// outside [0, 180), either not finite, min_track < 0
+int ba_filter_params_check(const ba_filter_params *p);
 
 // RCCL transport (ba_comm.cpp); comm is an ncclComm_t
 int ba_rccl_init(void **comm_out, const void *id128, int rank, int world);

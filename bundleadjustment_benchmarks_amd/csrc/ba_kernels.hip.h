@@ -233,7 +233,7 @@ template <typename T> struct ba_fuse_args {
     int *fresh;
     const unsigned short *cmask; // MASK: per camera, bit q = camera column q held constant (ba_solver_set_constant)
     const unsigned char *pfix;   // MASK: per point of the shard, != 0 = its three columns held constant
-    const T *wobs;               // MODEL: per observation of the shard (solver order), its weight; nullptr = all 1
+    const T *wobs;               // MODEL: per observation of the shard (solver order), its weight (0: inactive); nullptr = all 1
     int loss;                    // MODEL: ba_loss_kind (wave-uniform)
     T lscale;                    // MODEL: the loss's scale (tau / delta / c); its square travels in k_eval's tau2
 };
@@ -244,7 +244,7 @@ template <typename T> struct ba_fuse_args {
 //   de/dr = g (I - rh rh') + (rho' sqrt(s) / sqrt(rho)) rh rh' = g I + ((rho' - rho / s) / g) rh rh',   rh = r / sqrt(s)
 // (the chain rule of the lines below for rho = psi, rho' = W / 2).  ba_loss returns g and q = (rho' - rho / s) / g from closed forms of
 // rho / s that are finite at s = 0 (g -> sqrt(rho'(0)), q -> 0): nothing is divided by s below a kink.  The default model
-// (BA_LOSS_REFERENCE at 0.5 px without weights) never comes here: MODEL = false is the kernel as it was, the reference's clamps at
+// (BA_LOSS_REFERENCE at 0.5 px without weights and without an inactive observation) never comes here: MODEL = false is the kernel as it was, the reference's clamps at
 // |r| -> 0 included.
 #define BA_LOSS_K_REFERENCE 0
 #define BA_LOSS_K_TRIVIAL 1
@@ -336,6 +336,7 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
         const T kr = 1 + k1 * r2u + k2 * r4u;
         const T xd0 = kr * xu0, xd1 = kr * xu1;
         const T wo = (MODEL && fa.wobs) ? fa.wobs[i] : (T)1.0;
+        const bool off = MODEL && wo == (T)0; // inactive (ba_solver_set_obs_active: its effective weight is 0): see the end of this block
         const T r0 = MODEL ? wo * (f * xd0 - meas[i]) : f * xd0 - meas[i];
         const T r1 = MODEL ? wo * (f * xd1 - meas[(size_t)K + i]) : f * xd1 - meas[(size_t)K + i];
         const T r2 = r0 * r0 + r1 * r1;
@@ -422,6 +423,34 @@ __global__ __launch_bounds__(256) void k_eval(int K, int N, int Ml, const T *__r
                     Jp[(size_t)(q - 9) * K + i] = t0;
                     Jp[(size_t)(q - 6) * K + i] = t1;
                     if (FUSE > 0) { Bj[q - 9] = t0; Bj[q - 6] = t1; }
+                }
+            }
+        }
+        // An inactive observation is e = 0 and J = 0 by selection -- a product with 0 would leave the NaN of a projection that is not
+        // finite.  The zeros are written HERE, behind the arithmetic and its stores and over them, not selected inside the expressions
+        // above: a select there changed which products of a*b + c*d the compiler contracts, differently from one FUSE to the next in
+        // fp32 (their bit equality is tested) and from the kernels as they were.  Everything behind this point -- the energy sum, the
+        // fused point part, the records -- reads e2, ej, Aj and Bj.
+        if constexpr (MODEL) {
+            if (off) {
+                e2 = 0;
+                if (JAC) {
+                    ej[0] = 0; ej[1] = 0;
+                    r[i] = 0;
+                    r[(size_t)K + i] = 0;
+#pragma unroll
+                    for (int q = 0; q < 20; q++)
+                        if (!COOP) JcA[(size_t)i * 20 + q] = 0;
+#pragma unroll
+                    for (int q = 0; q < 18; q++) {
+                        if (SOA) Jc[(size_t)q * K + i] = 0;
+                        if (FUSE >= 2) Aj[q] = 0;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 6; q++) {
+                        Jp[(size_t)q * K + i] = 0;
+                        if (FUSE > 0) Bj[q] = 0;
+                    }
                 }
             }
         }

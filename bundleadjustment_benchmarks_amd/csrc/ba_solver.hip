@@ -18,6 +18,7 @@
 #include "ba_relpose.hip.h"
 #include "ba_dogleg.hip.h"
 #include "ba_triangulate.hip.h"
+#include "ba_filter.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -143,6 +144,9 @@ struct SolverBase {
     virtual int set_constant(const unsigned short *cam_mask, const unsigned char *pt_fixed) = 0;
     virtual int set_loss(int kind, double scale) = 0;
     virtual int set_obs_weights(const double *w) = 0;
+    virtual int set_obs_active(const unsigned char *active) = 0;
+    virtual int get_obs_active(unsigned char *active, long long *n_active) = 0;
+    virtual int filter(const ba_filter_params *p, int apply, unsigned char *obs_status, unsigned char *pt_status, double *err_px, ba_filter_stats *stats) = 0;
     virtual int set_priors(int type, int n, const int *ids, const double *x0, const double *info) = 0;
     virtual int prior_energy(double *out3) = 0;
     virtual int set_relposes(int n, const int *pairs, const double *R0, const double *t0, const double *Lr, const double *Lt) = 0;
@@ -320,6 +324,20 @@ template <typename T> struct Solver final : SolverBase {
         DevBuf<unsigned char> stat, fix; // [Ml] each
         size_t bytes() const { return bytes_of(ray) + bytes_of(part) + bytes_of(ids) + bytes_of(stat) + bytes_of(fix); }
     } tr;
+    struct Active { // ba_solver_set_obs_active / an applying ba_solver_filter_observations; allocated by the first inactive observation
+        DevBuf<unsigned char> act;        // [Kl] solver order, 1 = active
+        DevBuf<T> weff;                   // [Kl] the effective weight active ? w_o : 0: what k_eval reads in place of md.wobs while on()
+        std::vector<unsigned char> h_act; // the host's copy of act (empty: all active)
+        long long n_off = 0;
+        bool on() const { return n_off > 0; } // some observation is inactive
+        size_t bytes() const { return bytes_of(act) + bytes_of(weff); }
+    } ac;
+    struct Filter { // allocated by the first ba_solver_filter_observations
+        DevBuf<unsigned char> st, pst, nact; // observation statuses [Kl], point statuses [Ml], the new active bytes [Kl]
+        DevBuf<double> err, ray, part;       // [Kl]; [3][Kl]; [block partials: BA_FLT_NSUM tri_gmax() | the sums, padded to 16]
+        DevBuf<T> nweff;                     // [Kl] the new effective weights
+        size_t bytes() const { return bytes_of(st) + bytes_of(pst) + bytes_of(nact) + bytes_of(err) + bytes_of(ray) + bytes_of(part) + bytes_of(nweff); }
+    } fl;
     struct Cov { // allocated by the first ba_solver_covariance_compute
         DevBuf<T> buf; // the work buffer (cov_wp() ... cov_count() below)
         DevBuf<int> flag;
@@ -650,7 +668,7 @@ template <typename T> struct Solver final : SolverBase {
         fa.pt_ptr = d_pt_ptr.p; fa.lam = d_scal.p + SC_LAMBDA; fa.U0 = d_U0.p; fa.gp = d_gp.p;
         fa.rec = d_rec.p; fa.dinv = d_dinv.p; fa.tvec = d_tvec.p; fa.tri = d_tri.p; fa.fresh = &d_lm.p->rec_fresh;
         fa.cmask = mk.cmask.p; fa.pfix = mk.pfix.p;
-        fa.wobs = md.wobs.p; fa.loss = md.loss_kind; fa.lscale = md.loss_scale;
+        fa.wobs = ac.on() ? ac.weff.p : md.wobs.p; fa.loss = md.loss_kind; fa.lscale = md.loss_scale;
         // (CHOLESKY keeps the camera blocks in the AoS records alone: SOA = false, d_Jc is not even allocated)
         // eval_coop: the fused CHOLESKY linearisation stores its records a wavefront's run at a time (FUSE = 3 in place of 2) -- except in
         // fp32 on a problem of one round of workgroups, where it measured 2 % slower than the owners' stores (profiles/EXPERIMENTS.md, 7)
@@ -1459,7 +1477,7 @@ template <typename T> struct Solver final : SolverBase {
                               &d_pcg_z, &d_pcg_p, &d_pcg_y, &d_pcg_w})
             n += bytes_of(*b);
         n += bytes_of(d_chunk_info) + bytes_of(d_ent) + bytes_of(d_lm) + bytes_of(d_pcg_part) + bytes_of(d_pcg_part_s) + bytes_of(d_pcg) + mc_bytes();
-        return n + mk.bytes() + md.bytes() + pr.bytes() + rp.bytes() + dg.bytes() + tr.bytes() + cv.bytes() + fo.bytes() + sh.bytes();
+        return n + mk.bytes() + md.bytes() + pr.bytes() + rp.bytes() + dg.bytes() + tr.bytes() + ac.bytes() + fl.bytes() + cv.bytes() + fo.bytes() + sh.bytes();
     }
 
     // ---- covariance blocks (ba_solver_covariance_compute / _get; ba_cov.hip.h) -----------------------------------
@@ -1887,7 +1905,7 @@ template <typename T> struct Solver final : SolverBase {
     // Anything but the reference's psi at its 0.5 px without weights selects the MODEL instantiations of k_eval; nothing else changes
     // (everything downstream is built from e and J).  psi at another tau goes there too: the default kernels keep the reference's
     // clamps 1 / max(1e-15, .), which falsify dE/dr below |r|^2 = 1e-15, and the model's contract is a derivative that is right down to 0.  `tau` stays the reference's threshold: ba_solver_stats is its only other consumer.
-    bool model() const { return md.loss_kind != BA_LOSS_REFERENCE || md.loss_scale != (T)0.5 || md.wobs.p != nullptr; }
+    bool model() const { return md.loss_kind != BA_LOSS_REFERENCE || md.loss_scale != (T)0.5 || md.wobs.p != nullptr || ac.on(); }
     // the end of every setter that changes what a linearisation computes (mask, model, priors, constraints): the captured iterations
     // hold the other instantiations, kernel arguments and buffer addresses and are captured again on the next ba_minimize
     // (measurement: the loss or the weights, which triangulate() must not meet before a linearisation has taken them up)
@@ -1913,7 +1931,126 @@ template <typename T> struct Solver final : SolverBase {
             int rc;
             if ((rc = nw.upload(hw))) { (void)hipGetLastError(); return rc; }
         }
+        if (ac.on()) { // the mask stays: w_eff anew from the new weights
+            std::vector<T> he((size_t)Kl);
+            for (int i = 0; i < Kl; i++) he[i] = ac.h_act[i] ? (w ? (T)w[sx.perm[sx.o0 + i]] : (T)1.0) : (T)0;
+            HIPCHK(hipMemcpy(ac.weff.p, he.data(), sizeof(T) * he.size(), hipMemcpyHostToDevice));
+        }
         md.wobs = std::move(nw);
+        return model_changed(true);
+    }
+
+    // ---- the active mask and the filter (ba_solver_set_obs_active / ba_solver_filter_observations; ba_filter.hip.h)
+    // An inactive observation is an effective weight of 0, which the MODEL instantiations of k_eval select to e = 0, J = 0; nothing else
+    // changes (everything downstream is built from e and J).  Active ac: the bytes, w_eff and the host's copy; its device buffers are
+    // allocated once and stay (ac.on() says whether they are read).
+    bool active_refused() const { return !chol_elim() || sharded(); }
+    int active_alloc() // everything of Active that can fail
+    {
+        if (ac.act.p) return BA_OK;
+        DevBuf<unsigned char> na;
+        DevBuf<T> ne;
+        int rc;
+        if ((rc = na.alloc((size_t)(Kl > 0 ? Kl : 1))) || (rc = ne.alloc((size_t)(Kl > 0 ? Kl : 1)))) { (void)hipGetLastError(); return rc; }
+        ac.act = std::move(na); ac.weff = std::move(ne);
+        return BA_OK;
+    }
+    int set_obs_active(const unsigned char *active) override
+    {
+        if (active_refused()) return BA_ERR_ARG;
+        std::vector<unsigned char> ha;
+        long long off = 0;
+        if (active) {
+            ha.resize((size_t)Kl);
+            for (int i = 0; i < Kl; i++) { ha[i] = active[sx.perm[sx.o0 + i]] != 0; off += !ha[i]; }
+        }
+        if (off == 0) ha.clear();
+        if (ha == ac.h_act) return BA_OK; // the mask as it was: no flag changes
+        HIPCHK(hipStreamSynchronize(st));
+        if (off > 0) {
+            int rc;
+            if ((rc = active_alloc())) return rc;
+            std::vector<T> he((size_t)Kl, (T)1.0);
+            if (md.wobs.p) HIPCHK(hipMemcpy(he.data(), md.wobs.p, sizeof(T) * he.size(), hipMemcpyDeviceToHost));
+            for (int i = 0; i < Kl; i++) if (!ha[i]) he[i] = (T)0;
+            HIPCHK(hipMemcpy(ac.act.p, ha.data(), ha.size(), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(ac.weff.p, he.data(), sizeof(T) * he.size(), hipMemcpyHostToDevice));
+        }
+        ac.h_act = std::move(ha);
+        ac.n_off = off;
+        return model_changed(true);
+    }
+    int get_obs_active(unsigned char *active, long long *n_active) override
+    {
+        for (int i = 0; active && i < Kl; i++) active[sx.perm[sx.o0 + i]] = ac.on() ? ac.h_act[i] : 1;
+        if (n_active) *n_active = (long long)Kl - ac.n_off;
+        return BA_OK;
+    }
+    int filter(const ba_filter_params *pp, int apply, unsigned char *obs_status, unsigned char *pt_status, double *err_px, ba_filter_stats *stats) override
+    {
+        ba_filter_params fp;
+        if (pp) fp = *pp; else ba_filter_params_default(&fp);
+        if (active_refused() || ba_filter_params_check(&fp)) return BA_ERR_ARG;
+        int rc;
+        if (!fl.part.p) { // everything that can fail first: the solver is unchanged behind an error
+            Filter nf;
+            const size_t k1 = (size_t)(Kl > 0 ? Kl : 1), m1 = (size_t)(Ml > 0 ? Ml : 1);
+            if ((rc = nf.st.alloc(k1)) || (rc = nf.pst.alloc(m1)) || (rc = nf.nact.alloc(k1)) || (rc = nf.err.alloc(k1)) || (rc = nf.ray.alloc(3 * k1)) ||
+                (rc = nf.part.alloc((size_t)BA_FLT_NSUM * tri_gmax() + 16)) || (rc = nf.nweff.alloc(k1))) { (void)hipGetLastError(); return rc; }
+            HIPCHK(hipMemset(nf.part.p, 0, sizeof(double) * nf.part.n));
+            fl = std::move(nf);
+        }
+        if (apply && (rc = active_alloc())) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        const double amin = fp.min_angle_deg * (M_PI / 180.0);
+        const ba_flt_cfg cf{fp.max_reproj_px, amin, ba_flt_chord2_exit(amin), fp.min_track, fp.require_front != 0};
+        const int g = tri_gmax();
+        double *sums = fl.part.p + (size_t)BA_FLT_NSUM * g;
+        const unsigned char *act = ac.on() ? (const unsigned char *)ac.act.p : nullptr;
+        HIPCHK(hipEventRecord(ev[EV_T0], st));
+        hipLaunchKernelGGL((k_filter_obs<T, TRI_LANES>), dim3(g), dim3(256), 0, st, N, Ml, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
+                           (const T *)d_cam[0].p, (const T *)d_pts[0].p, (const T *)d_meas.p, act, cf, fl.st.p, fl.err.p, fl.ray.p);
+        hipLaunchKernelGGL((k_filter_points<T, TRI_LANES>), dim3(g), dim3(256), 0, st, Ml, Kl, (const int *)d_pt_ptr.p, cf, fl.st.p, (const double *)fl.err.p,
+                           (const double *)fl.ray.p, (const T *)md.wobs.p, fl.pst.p, apply ? fl.nact.p : (unsigned char *)nullptr,
+                           apply ? fl.nweff.p : (T *)nullptr, fl.part.p);
+        ba_red_jobs jobs{};
+        for (int k = 0; k < 8; k++) jobs.j[k] = {fl.part.p + (size_t)k * g, g, 0, k};
+        hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(8), dim3(256), 0, st, jobs, sums, (const int *)nullptr, (long long *)nullptr);
+        ba_red_jobs jobs2{};
+        for (int k = 0; k < 2; k++) jobs2.j[k] = {fl.part.p + (size_t)(8 + k) * g, g, 0, 8 + k};
+        hipLaunchKernelGGL((k_reduce_scalars<double>), dim3(2), dim3(256), 0, st, jobs2, sums, (const int *)nullptr, (long long *)nullptr);
+        HIPCHK(hipEventRecord(ev[EV_T1], st));
+        double h[BA_FLT_NSUM];
+        HIPCHK(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        ba_filter_stats fs{};
+        for (int k = 0; k < 6; k++) fs.by_status[k] = (long long)h[k];
+        fs.points_short = (long long)h[6]; fs.points_low_angle = (long long)h[7];
+        fs.err_sum_before = h[8]; fs.err_sum_after = h[9];
+        fs.active_before = (long long)Kl - fs.by_status[BA_OBS_WAS_OFF];
+        fs.active_after = fs.by_status[BA_OBS_KEPT];
+        fs.ms = ev_ms(EV_T0, EV_T1);
+        // the outputs in file order, as set_obs_weights takes its input
+        if (obs_status) {
+            std::vector<unsigned char> hs((size_t)Kl);
+            if (Kl) HIPCHK(hipMemcpy(hs.data(), fl.st.p, hs.size(), hipMemcpyDeviceToHost));
+            for (int i = 0; i < Kl; i++) obs_status[sx.perm[sx.o0 + i]] = hs[i];
+        }
+        if (err_px) {
+            std::vector<double> he((size_t)Kl);
+            if (Kl) HIPCHK(hipMemcpy(he.data(), fl.err.p, sizeof(double) * he.size(), hipMemcpyDeviceToHost));
+            for (int i = 0; i < Kl; i++) err_px[sx.perm[sx.o0 + i]] = he[i];
+        }
+        if (pt_status && Ml) HIPCHK(hipMemcpy(pt_status, fl.pst.p, (size_t)Ml, hipMemcpyDeviceToHost));
+        if (stats) *stats = fs;
+        if (!apply || fs.active_after == fs.active_before) return BA_OK; // a measurement, or nothing deactivated: every bit and flag stays
+        std::vector<unsigned char> ha((size_t)Kl);
+        HIPCHK(hipMemcpy(ha.data(), fl.nact.p, ha.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ac.act.p, fl.nact.p, ha.size(), hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(ac.weff.p, fl.nweff.p, sizeof(T) * ha.size(), hipMemcpyDeviceToDevice));
+        ac.h_act = std::move(ha);
+        ac.n_off = (long long)Kl - fs.active_after;
         return model_changed(true);
     }
 
@@ -2432,10 +2569,12 @@ template <typename T> struct Solver final : SolverBase {
             const ba_tri_cfg cf{tp.min_angle_deg * (M_PI / 180.0), tp.max_reproj_px, tp.refine_iters, tp.only_if_better, md.loss_kind, (double)md.loss_scale};
             double *sums = tr.part.p + (size_t)TRI_NSUM * tri_gmax();
             HIPCHK(hipEventRecord(ev[EV_T0], st));
+            // (an inactive observation is not part of its track; no mask: a null pointer)
+            const unsigned char *act = ac.on() ? (const unsigned char *)ac.act.p : nullptr;
             hipLaunchKernelGGL((k_tri_rays<T, TRI_LANES>), dim3(g), dim3(256), 0, st, n, ids, N, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
-                               (const T *)d_cam[0].p, (const T *)d_meas.p, tr.ray.p);
+                               (const T *)d_cam[0].p, (const T *)d_meas.p, act, tr.ray.p);
             hipLaunchKernelGGL((k_tri_points<T, TRI_LANES>), dim3(g), dim3(256), 0, st, n, ids, N, Ml, Kl, (const int *)d_pt_ptr.p, (const int *)d_obs_cam.p,
-                               (const T *)d_cam[0].p, (const T *)d_meas.p, (const T *)md.wobs.p, (const double *)tr.ray.p,
+                               (const T *)d_cam[0].p, (const T *)d_meas.p, (const T *)md.wobs.p, act, (const double *)tr.ray.p,
                                any_fix ? (const unsigned char *)tr.fix.p : (const unsigned char *)nullptr, cf, d_pts[0].p, tr.stat.p, tr.part.p);
             ba_red_jobs jobs{};
             for (int k = 0; k < 8; k++) jobs.j[k] = {tr.part.p + (size_t)k * g, g, 0, k};
@@ -3153,6 +3292,16 @@ int ba_solver_set_constant(ba_solver *s, const unsigned short *cam_mask, const u
 }
 int ba_solver_set_loss(ba_solver *s, int kind, double scale) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_loss(kind, scale); }
 int ba_solver_set_obs_weights(ba_solver *s, const double *w) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_obs_weights(w); }
+int ba_solver_set_obs_active(ba_solver *s, const unsigned char *active) { return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_obs_active(active); }
+int ba_solver_get_obs_active(ba_solver *s, unsigned char *active, long long *n_active)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->get_obs_active(active, n_active);
+}
+int ba_solver_filter_observations(ba_solver *s, const ba_filter_params *p, int apply, unsigned char *obs_status, unsigned char *pt_status, double *err_px,
+                                  ba_filter_stats *stats)
+{
+    return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->filter(p, apply, obs_status, pt_status, err_px, stats);
+}
 int ba_solver_set_point_priors(ba_solver *s, int n, const int *pt_ids, const double *x0, const double *sqrt_info)
 {
     return !s ? BA_ERR_ARG : !BA_LIVE(s) ? BA_ERR_HIP : s->impl->set_priors(0, n, pt_ids, x0, sqrt_info);

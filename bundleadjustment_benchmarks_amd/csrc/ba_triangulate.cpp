@@ -18,6 +18,7 @@ struct HostObs {
         o.w = w ? w[i] : 1.0;
     }
     void ray(int i, double d[3]) const { for (int k = 0; k < 3; k++) d[k] = rays[3 * (size_t)i + k]; }
+    bool active(int) const { return true; } // (the caller passes the active observations)
 };
 struct HostRed {
     double sum(double v) const { return v; }

@@ -127,6 +127,7 @@ BA_TRI_HD void ba_tri_pass(int lane, int t, const Obs &ob, const Red &rd, int lo
 {
     double c = 0.0, H[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, maxrep = 0.0, behind = 0.0;
     for (int i = lane; i < t; i += L) {
+        if (!ob.active(i)) continue; // (ba_solver_set_obs_active: not part of the track)
         ba_tri_obs o;
         ob.load(i, o);
         const double *R = o.c;
@@ -186,7 +187,7 @@ BA_TRI_HD void ba_tri_point(int lane, int t, const Obs &ob, const Red &rd, const
     if (fixed) { out.status = BA_TRI_K_FIXED; return; }
     // 2. the largest angle between two usable rays: the largest chord |d_i - d_j|, theta = 2 atan2(chord, sqrt(4 - chord^2))
     double nus = 0.0, c2max = 0.0;
-    for (int i = lane; i < t; i += L) {
+    for (int i = lane; i < t; i += L) { // (an inactive observation has no ray)
         double di[3];
         ob.ray(i, di);
         if (di[0] == 0.0 && di[1] == 0.0 && di[2] == 0.0) continue;
@@ -268,6 +269,8 @@ template <typename T> struct ba_tri_obs_dev {
     const T *cam, *meas, *wobs;
     const int *obs_cam;
     const double *rays; // [3][K], by observation; zeros = unusable
+    const unsigned char *act; // by observation, 0 = inactive (ba_solver_set_obs_active); nullptr = all active
+    __device__ bool active(int i) const { return !act || act[o0 + i] != 0; }
     __device__ void load(int i, ba_tri_obs &o) const
     {
         const int q = o0 + i, a = obs_cam[q];
@@ -287,18 +290,20 @@ template <typename T> struct ba_tri_obs_dev {
 template <typename T, int L>
 __global__ __launch_bounds__(256) void k_tri_rays(int n, const int *__restrict__ ids, int N, int K, const int *__restrict__ pt_ptr,
                                                   const int *__restrict__ obs_cam, const T *__restrict__ cam, const T *__restrict__ meas,
-                                                  double *__restrict__ rays)
+                                                  const unsigned char *__restrict__ act, double *__restrict__ rays)
 {
     const int q = (int)((blockIdx.x * 256u + threadIdx.x) / L), lane = threadIdx.x % L;
     if (q >= n) return;
     const int j = ids ? ids[q] : q;
-    const ba_tri_obs_dev<T> ob{N, K, 0, cam, meas, nullptr, obs_cam, nullptr};
+    const ba_tri_obs_dev<T> ob{N, K, 0, cam, meas, nullptr, obs_cam, nullptr, act};
     const int e = pt_ptr[j + 1];
     for (int i = pt_ptr[j] + lane; i < e; i += L) {
-        ba_tri_obs o;
-        ob.load(i, o);
-        double d[3];
-        (void)ba_tri_ray(o, d);
+        double d[3] = {0.0, 0.0, 0.0};
+        if (ob.active(i)) {
+            ba_tri_obs o;
+            ob.load(i, o);
+            (void)ba_tri_ray(o, d);
+        }
         rays[i] = d[0]; rays[(size_t)K + i] = d[1]; rays[2 * (size_t)K + i] = d[2];
     }
 }
@@ -308,8 +313,8 @@ __global__ __launch_bounds__(256) void k_tri_rays(int n, const int *__restrict__
 template <typename T, int L>
 __global__ __launch_bounds__(256) void k_tri_points(int n, const int *__restrict__ ids, int N, int M, int K, const int *__restrict__ pt_ptr,
                                                     const int *__restrict__ obs_cam, const T *__restrict__ cam, const T *__restrict__ meas,
-                                                    const T *__restrict__ wobs, const double *__restrict__ rays,
-                                                    const unsigned char *__restrict__ fixed, ba_tri_cfg cf, T *__restrict__ pts,
+                                                    const T *__restrict__ wobs, const unsigned char *__restrict__ act,
+                                                    const double *__restrict__ rays, const unsigned char *__restrict__ fixed, ba_tri_cfg cf, T *__restrict__ pts,
                                                     unsigned char *__restrict__ status, double *__restrict__ part)
 {
     constexpr int G = 256 / L;
@@ -319,7 +324,7 @@ __global__ __launch_bounds__(256) void k_tri_points(int n, const int *__restrict
     if (q < n) {
         const int j = ids ? ids[q] : q;
         const int o0 = pt_ptr[j], t = pt_ptr[j + 1] - o0;
-        const ba_tri_obs_dev<T> ob{N, K, o0, cam, meas, wobs, obs_cam, rays};
+        const ba_tri_obs_dev<T> ob{N, K, o0, cam, meas, wobs, obs_cam, rays, act};
         const double xold[3] = {(double)pts[j], (double)pts[(size_t)M + j], (double)pts[2 * (size_t)M + j]};
         ba_tri_out out;
         ba_tri_point<L>(lane, t, ob, ba_tri_red_dev<L>{}, cf, xold, fixed ? (int)fixed[j] : 0, out);

@@ -789,6 +789,83 @@ int ba_triangulate_point(int t, const double *cam15, const double *meas, const d
                          const ba_triangulate_params *p, const double *x_old, double *x_new, int *status, double *cost_old,
                          double *cost_new, double *angle_deg);
 
+/* ---- the active mask and the observation filter (no reference counterpart; COLMAP's FilterObservations / FilterPoints between
+ * bundle-adjustment rounds, Ceres users rebuild the problem) --------------------------------------------------- */
+
+/* ba_solver_set_obs_active: an INACTIVE observation contributes exactly +0 to e and to its rows of J -- by selection, not by a product
+ * with 0, so also where its projection is not finite (a point on the camera's principal plane, an inf).  Everything built from e and J
+ * follows, as for the weights above: energy, g, U, V, S, rhs, lambda0, rho, the stop tests, BA_ITERSCHUR's operator and its
+ * preconditioners, Marquardt's D, the dogleg's q, both covariances.  BA_GET_RESIDUALS, BA_GET_JC and BA_GET_JP return zeros at an inactive
+ * observation.  ba_solver_stats keeps its meaning (all K observations); ba_problem_covisibility and the visibility forest's plan are
+ * functions of the problem and do not change.
+ * active: K bytes of the PROBLEM in the order of the input file, != 0 = active; NULL = all active; copied.  The solver keeps the
+ * effective weight w_eff = active ? w_o : 0 as one device array in its own observation order; the weights and the mask stay independent
+ * settings: ba_solver_set_obs_weights(NULL) keeps the mask, ba_solver_set_obs_active(NULL) keeps the weights.  While an observation is
+ * inactive the solver runs the measurement model's instantiations of the linearisation; a mask that is NULL or all non-zero restores the
+ * path without one bit for bit (with the default loss and no weights: the default kernels).
+ * A point whose observations are all inactive behaves as a point nobody observes: U = lambda I (lambda diag_min under Marquardt), a step
+ * of exactly 0, its bits kept; at lambda = 0 the covariance calls return BA_ERR_SINGULAR for it unless it is held constant.  A camera
+ * with no active observation: the same on its 9 x 9 block.
+ * State: as ba_solver_set_obs_weights -- the change takes effect at the next ba_solver_linearize or ba_minimize, a ba_solver_try_step
+ * before that returns BA_ERR_ARG, a computed covariance and a prepared dogleg become stale, ba_solver_triangulate_points refuses until a
+ * linearisation has taken the mask up.  A call that leaves the mask as it was (the same bytes after != 0) changes no flag.
+ * ba_solver_triangulate_points under a mask: an inactive observation is not part of its track (no ray, not in the angle, the midpoint,
+ * the refinement's cost, cost_before / cost_after, the front test or the max_reproj_px test); fewer than two active usable
+ * observations: BA_TRI_FEW_VIEWS.
+ * BA_ERR_ARG, the solver unchanged: a kind other than BA_CHOLESKY or BA_ITERSCHUR (an emptied track would put a zero column block into
+ * the per-point QR: not built); shard_world > 1 (not built).
+ * Memory, allocated by the first mask with an inactive observation (or the first applying filter call), kept until ba_solver_free and
+ * counted by ba_solver_device_bytes: K (1 + sizeof(scalar)) bytes -- the active bytes and w_eff. */
+int ba_solver_set_obs_active(ba_solver *s, const unsigned char *active /* K of the PROBLEM, file order; != 0 = active; NULL = all */);
+/* active (may be NULL) receives K bytes 0 / 1 in file order, n_active (may be NULL) their sum.  Every kind; all ones where no mask can be set. */
+int ba_solver_get_obs_active(ba_solver *s, unsigned char *active /* K, file order */, long long *n_active);
+
+/* The filter.  Per point, on the resident state x (model and fp64 geometry as for the triangulation above: XX = R X + T, in front iff
+ * XX_2 < 0, the state read as stored), one text for the host function and the kernels (csrc/ba_filter.hip.h):
+ * 1. An observation that is already inactive is BA_OBS_WAS_OFF and takes no further part.
+ * 2. Per active observation: BA_OBS_BEHIND if require_front and not (XX_2 < 0) (a NaN counts as behind); otherwise, with
+ *    err = |pi(X) - meas| (unweighted, pixels): BA_OBS_NONFINITE if err is not finite, BA_OBS_REPROJ if max_reproj_px > 0 and
+ *    err > max_reproj_px.  The others are survivors.
+ * 3. Fewer than min_track survivors: the point is BA_FPT_SHORT.
+ * 4. With min_angle_deg > 0 and the point not short: theta = the largest angle between two survivors' rays d_o = (C_o - X) / |C_o - X|,
+ *    C_o = -R'T -- the rays of the CURRENT point, as COLMAP takes them --, from the largest chord: theta = 2 atan2(c, sqrt(4 - c^2)),
+ *    c = max |d_i - d_j|.  A survivor with |C_o - X| = 0 or not finite has no ray.  theta < min_angle_deg: BA_FPT_LOW_ANGLE.  (The kernel
+ *    needs the decision only and leaves a lane's pair loop at a chord that decides it; ba_filter_track returns the full theta.)
+ * 5. Every survivor of a point that is not kept becomes BA_OBS_POINT.
+ * 6. apply != 0: every observation whose status is not BA_OBS_KEPT becomes inactive, w_eff rewritten on the device by the same launch;
+ *    if at least one was deactivated the state changes exactly as with ba_solver_set_obs_active, otherwise it keeps every bit and every
+ *    flag.  apply == 0: a measurement; nothing changes, not even a flag.
+ * Points held constant or carrying a prior are filtered like any other: their observations constrain cameras.
+ * err_px: |pi - meas| of every active observation, whatever the arithmetic gives (BEHIND ones too); NaN at BA_OBS_WAS_OFF.
+ * A point's statuses are the same bits on every run; no atomics. */
+typedef enum { BA_OBS_KEPT = 0, BA_OBS_WAS_OFF = 1, BA_OBS_BEHIND = 2, BA_OBS_NONFINITE = 3, BA_OBS_REPROJ = 4, BA_OBS_POINT = 5 } ba_obs_status;
+typedef enum { BA_FPT_KEPT = 0, BA_FPT_SHORT = 1, BA_FPT_LOW_ANGLE = 2 } ba_filter_point_status;
+typedef struct { double max_reproj_px; double min_angle_deg; int min_track; int require_front; } ba_filter_params;
+void ba_filter_params_default(ba_filter_params *p); /* 4.0 (COLMAP's filter_max_reproj_error), 1.5 (its min_tri_angle), 2, 1 */
+/* active_before = K - by_status[BA_OBS_WAS_OFF], active_after = by_status[BA_OBS_KEPT]; err_sum_before: sum of err_px over the active
+ * observations with a finite err_px, err_sum_after: over the kept ones; fp64, lane sums combined by a fixed butterfly per point, block
+ * partials of 32 points reduced in a fixed order.  ms: device time of the call's launches. */
+typedef struct {
+    long long active_before, active_after, by_status[6], points_short, points_low_angle;
+    double err_sum_before, err_sum_after;
+    double ms;
+} ba_filter_stats;
+/* ba_solver_filter_observations: the rule for all points.  obs_status (K bytes, file order), pt_status (M bytes), err_px (K doubles, file
+ * order), stats: any may be NULL; p == NULL means the defaults.  BA_CHOLESKY and BA_ITERSCHUR, BA_F64 and BA_F32, shard_world == 1.
+ * BA_ERR_ARG, decided on the host, the solver unchanged: another kind, a sharded solver (neither built); max_reproj_px < 0 or not
+ * finite; min_angle_deg outside [0, 180) or not finite; min_track < 0.
+ * Memory, allocated by the first call, kept until ba_solver_free and counted by ba_solver_device_bytes:
+ *   K (34 + sizeof(scalar)) (status 1, err_px 8, rays 24, the new active bytes 1, the new w_eff) + M (point status)
+ *   + 8 (10 max(1, ceil(8 M / 256)) + 16) bytes; a call with apply != 0 also allocates the mask's K (1 + sizeof(scalar)) above.
+ * BA_ERR_NOMEM when they do not fit; the solver stays usable. */
+int ba_solver_filter_observations(ba_solver *s, const ba_filter_params *p, int apply, unsigned char *obs_status /* K, file order */,
+                                  unsigned char *pt_status /* M */, double *err_px /* K, file order */, ba_filter_stats *stats);
+/* ba_filter_track: the rule on one track, host only (no GPU).  cam15: 15 t (one BA_GET_CAMS row per observation), meas: 2 t, active: t
+ * bytes or NULL (all active), X: the point.  obs_status: t bytes, err_px: t, angle_deg: the full theta (0 where step 4 did not run).
+ * Any output pointer may be NULL; p == NULL: the defaults.  BA_ERR_ARG: t < 0, a missing array, parameters as above. */
+int ba_filter_track(int t, const double *cam15, const double *meas, const unsigned char *active, const double *X,
+                    const ba_filter_params *p, unsigned char *obs_status, int *pt_status, double *err_px, double *angle_deg);
+
 /* Library / device info: fills name (<= n bytes), returns the number of CUs via *cus. */
 int ba_device_info(int device, char *name, size_t n, int *cus);
 const char *ba_version(void);
